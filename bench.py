@@ -15,12 +15,18 @@ The RCCL all-gather that reassembles the maps (the north_star's only collective)
 separately (``allgather_ms``), and so is the row-chunked fit with each chunk's all-gather
 overlapped with the next chunk's fit (``fit_allgather_overlapped_ms``).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--weak]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3] [--weak] [--dump-outputs DIR] [--full]
 
-Rank 0 prints one JSON line.  It carries ``roofline`` (kernel time = median of 50 HIP-event
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps and prints the headline
+figures only (``value``, ``ms_per_step``, ...).  ``--dump-outputs DIR`` also writes what the last timed step
+computed as ``DIR/<name>.npy`` (float32/float64; a fixed seeded pixel sample of outputs over 48 MiB), so two
+builds can be compared output for output: with the same arguments the inputs are identical from run to run.
+
+``--full`` adds every other leg.  The line then carries ``roofline`` (kernel time = median of 50 HIP-event
 windows on the launch stream after 10 warm-ups, each window ≥ 1 ms of back-to-back launches), an in-run ``parity`` check of sampled outputs
 against the CPU oracle (BASELINE.md plan step 5) and ``cpu_baseline`` (rank 0, N = 1: the
-oracle's NumPy restatement on a bounded sample, at the affinity thread count and at 1 thread).
+oracle's NumPy restatement on a bounded sample, at the affinity thread count and at 1 thread), and at
+N > 1 the all-gather legs.
 """
 from __future__ import annotations
 
@@ -289,6 +295,32 @@ class Workload:
         t = self.traffic()
         return t if isinstance(t, tuple) else (t, None)
 
+    def outputs(self, last):
+        """What step(last) left for its caller: [(name, device tensor, pixel axis or None)]."""
+        raise NotImplementedError
+
+
+DUMP_BUDGET = 48 * 2 ** 20  # bytes of .npy payload per run (all ranks together)
+
+
+def dump_outputs(wl, ctx, last, outdir):
+    """Write this rank's outputs of step `last` as outdir/<name>.npy (rank suffix at N > 1): floating outputs
+    as float32, integer ones as float64 (exact).  Arrays with a pixel axis are cut to the same fixed sample
+    of pixels (sample_idx, seed 12345) when all of them together exceed this rank's share of DUMP_BUDGET."""
+    outs = wl.outputs(last)
+    width = lambda t: 4 if t.is_floating_point() and t.element_size() <= 4 else 8  # noqa: E731
+    per_px = sum(width(t) * (t.numel() // wl.P) for _, t, ax in outs if ax is not None)
+    fixed = sum(width(t) * t.numel() for _, t, ax in outs if ax is None)
+    n = max(1, min(wl.P, (DUMP_BUDGET // ctx.world - fixed) // max(per_px, 1)))
+    idx = torch_idx(sample_idx(wl.P, n, 12345), ctx.dev) if n < wl.P else None
+    os.makedirs(outdir, exist_ok=True)
+    for name, t, ax in outs:
+        if ax is not None and idx is not None:
+            t = t.index_select(ax, idx)
+        a = t.cpu().numpy()
+        a = a.astype(np.float32 if width(t) == 4 else np.float64)
+        np.save(os.path.join(outdir, name + (f"_rank{ctx.rank}" if ctx.world > 1 else "") + ".npy"), a)
+
 
 class FitWorkload(Workload):
     """One step = one rti_fit_shared call (launches_per_step launches) over this rank's row block."""
@@ -374,6 +406,9 @@ class FitWorkload(Workload):
             ("-pm" if self.stack == "pixel" else "")
         fam = f"fit_{self.u8_kernel}" if self.u8_kernel else ("fit_pm" if self.stack == "pixel" else None)
         return load_traffic(key, fam)
+
+    def outputs(self, last):
+        return [("coef", self.coef, 1 if self.args.layout == "pixel" else 2)]
 
     def config(self):
         cfg = {"lights": self.N, "channels": self.C, "basis": self.basis, "k": self.k,
@@ -477,6 +512,9 @@ class FitResidualWorkload(FitWorkload):
             return None
         return load_traffic(self.args.config)
 
+    def outputs(self, last):
+        return super().outputs(last) + [("residual", self.res, 1), ("residual_energy_partial", self.partial, None)]
+
     def parity(self):
         o = oracle()
         idx = sample_idx(self.P, 4096, 13 + self.ctx.rank)
@@ -541,6 +579,9 @@ class RelightWorkload(Workload):
                                   self.stream)
         if st:
             L.check(st, "rti_relight")
+
+    def outputs(self, last):
+        return [("image", self.outs[last % self.sets], 0)]
 
     def config(self):
         return {"evals": self.E, "basis": self.basis, "k": self.k, "coef_layout": "pixel", "out": "f32",
@@ -610,6 +651,9 @@ class FrameWorkload(RelightWorkload):
                                         self.stream)
         if st:
             L.check(st, "rti_relight_frame")
+
+    def outputs(self, last):
+        return [("bgr", self.bgrs[last % self.sets], 0)]
 
     def config(self):
         c = super().config()
@@ -693,6 +737,9 @@ class PerPixelWorkload(Workload):
 
         self.step = step
 
+    def outputs(self, last):
+        return [("coef", self.coef, 0)]
+
     def config(self):
         return {"lights": self.N, "basis": "ptm", "k": 6, "coef_layout": "pixel", "geometry": "per-pixel cameras"}
 
@@ -773,6 +820,9 @@ class OperatorWorkload(Workload):
                                          c.c_void_p(self.out.data_ptr()), L.RTI_I32, self.P, self.E * self.P, self.stream)
         if st:
             L.check(st, "rti_apply_operator")
+
+    def outputs(self, last):
+        return [("tables", self.out, 1)]
 
     def config(self):
         return {"lights": self.N, "evals": self.E, "basis": "rbf-linear", "out": "int32 tables [E][P]",
@@ -877,9 +927,14 @@ class RbfPerPixelWorkload(Workload):
         torch.cuda.synchronize(self.I.device)
         return int(cnt.item())
 
+    def outputs(self, last):
+        return [("tables", self.out, 1), ("status", self.status, None)]
+
     def config(self):
-        return {"lights": self.N, "evals": self.E, "basis": "rbf-linear per-pixel", "out": "int32 tables [E][P]",
-                "fallback_px": self.fallback_px()}
+        cfg = {"lights": self.N, "evals": self.E, "basis": "rbf-linear per-pixel", "out": "int32 tables [E][P]"}
+        if getattr(self.args, "full", False):  # counting the fallback pixels takes a step of its own
+            cfg["fallback_px"] = self.fallback_px()
+        return cfg
 
     def roofline(self, kernel_ms):
         ach = self.flops / (kernel_ms * 1e-3) / 1e12
@@ -1124,9 +1179,15 @@ def parse_args(argv=None):
                     help="c7: operator as two fp16 halves on f16 MFMA (default) or fp32 on f32 MFMA")
     ap.add_argument("--map-sets", type=int, default=3,
                     help="c5/c9: coefficient-map sets rotated over launches (3 = HBM-cold, 1 = L3-resident)")
-    ap.add_argument("--no-allgather", action="store_true", help="N>1: skip the RCCL all-gather legs")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-parity", action="store_true", help="skip the in-run parity check")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the event-timed kernel/roofline passes, the in-run parity "
+                         "check, the CPU baseline and (N>1) the all-gather legs, and report them in the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32/float64; a fixed "
+                         "seeded pixel sample of outputs over 48 MiB)")
+    ap.add_argument("--no-allgather", action="store_true", help="--full, N>1: skip the RCCL all-gather legs")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-parity", action="store_true", help="--full: skip the in-run parity check")
     ap.add_argument("--cpu-budget", type=float, default=16.0, help="seconds of CPU baseline (half per thread count)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL) for real runs; gloo lets ranks share one GPU in rehearsals")
@@ -1135,6 +1196,32 @@ def parse_args(argv=None):
     ap.add_argument("--plan", action="store_true",
                     help="print the rank/row plan only (no device work; CPU tests of the launcher)")
     return ap.parse_args(argv)
+
+
+def headline(wl, ctx, args, elapsed, dev):
+    """The result line of a plain run: the timed region's figures (elapsed = the max over ranks)."""
+    conf = {"workload": wl.desc, "H": ctx.H, "W": wl.W, "H_per_rank": ctx.h}
+    conf.update(wl.config())
+    conf["parallelism"] = (f"row-tiled x{ctx.world}: rank r fits rows [r*H/G, (r+1)*H/G) of one {ctx.H}-row image"
+                           if not args.weak else f"row-tiled x{ctx.world}: one {ctx.h}-row image per GPU (weak)")
+    return {
+        "metric": wl.metric,
+        "value": round(wl.total_units * args.steps / elapsed / 1e6, 1),
+        "unit": wl.unit,
+        "n_gpus": ctx.world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak" if args.weak else "strong",
+        "vs_baseline": None,
+        "dtype": wl.dtype,
+        "data": "synthetic (seeded smooth PTM/HSH coefficient fields + N(0,2) noise, rounded to 0..255, fp32)",
+        "config": conf,
+        "timed_region_ms": round(elapsed * 1e3, 3),
+        "full": bool(args.full),
+        "device": device_info(dev),
+    }
 
 
 def main():
@@ -1216,6 +1303,17 @@ def main():
     if world > 1:
         dist.barrier()
 
+    if args.dump_outputs:
+        dump_outputs(wl, ctx, args.steps - 1, args.dump_outputs)
+    if not args.full:  # the headline figures only
+        if world > 1:
+            elapsed = reduce_max([elapsed], ctx, backend)[0]
+        if rank == 0:
+            print(json.dumps(headline(wl, ctx, args, elapsed, dev)), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
     # per-launch spread (kernel_ms_stats): HIP events around each launch on the launch stream,
     # 10 warm-ups then 50 pairs, in a separate pass so the events add no gaps above
     for i in range(10):
@@ -1264,33 +1362,15 @@ def main():
         gather_ms, e2e_ms = reduce_max([gather_ms, e2e_ms if e2e_ms is not None else 0.0], ctx, backend)
         e2e_ms = e2e_ms or None
 
-    value = wl.total_units * args.steps / elapsed / 1e6
     cpu = None
     if rank == 0 and world == 1 and not args.no_cpu:
         cpu = cpu_baseline(wl, args.cpu_budget)
     if rank == 0:
-        conf = {"workload": wl.desc, "H": ctx.H, "W": wl.W, "H_per_rank": ctx.h}
-        conf.update(wl.config())
-        conf["parallelism"] = (f"row-tiled x{world}: rank r fits rows [r*H/G, (r+1)*H/G) of one {ctx.H}-row image"
-                               if not args.weak else f"row-tiled x{world}: one {ctx.h}-row image per GPU (weak)")
-        line = {
-            "metric": wl.metric,
-            "value": round(value, 1),
-            "unit": wl.unit,
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak" if args.weak else "strong",
-            "vs_baseline": None,
-            "dtype": wl.dtype,
-            "data": "synthetic (seeded smooth PTM/HSH coefficient fields + N(0,2) noise, rounded to 0..255, fp32)",
-            "config": conf,
+        line = headline(wl, ctx, args, elapsed, dev)
+        line.update({
             # the same work over the event-timed kernel time (median of 50 windows of >= 1 ms): a timed region of
             # K short steps carries the launch/sync overhead of its first and last step, this figure does not
             "value_kernel": round(wl.total_units / (kernel_ms * 1e-3) / 1e6, 1),
-            "timed_region_ms": round(elapsed * 1e3, 3),
             "roofline": wl.roofline(kernel_ms),
             "kernel_ms_stats": {"median": round(kernel_ms, 5), "min": round(float(wms.min()), 5),
                                 "mean": round(float(wms.mean()), 5), "n": 50, "launches_per_window": m,
@@ -1300,8 +1380,7 @@ def main():
                                 "per_rank_median": [round(x, 5) for x in kernel_ms_rank]},
             "parity": parity,
             "cpu_baseline": cpu,
-            "device": device_info(dev),
-        }
+        })
         if gather_ms is not None:
             line["allgather_ms"] = round(gather_ms, 3)
             if e2e_ms is not None:

@@ -8,9 +8,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "smartphone-based-rti_amd")
 ORACLE = os.path.join(ROOT, "oracle")
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-for p in (PKG, ORACLE):
+for p in (PKG, ORACLE, GOLDEN):
     if p not in sys.path:
         sys.path.insert(0, p)
+
+import golden_parts  # noqa: E402  (tests/golden: vectors over 1 MiB are stored as part files)
 
 
 def pytest_configure(config):
@@ -19,7 +21,7 @@ def pytest_configure(config):
 
 
 def golden(name):
-    return np.load(os.path.join(GOLDEN, name), allow_pickle=False)
+    return golden_parts.load(os.path.join(GOLDEN, name))
 
 
 def coef_close(got, ref, rtol=1e-4):

@@ -23,6 +23,9 @@ import contextlib
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+
+import golden_parts  # noqa: E402  (vectors over 1 MiB are written as part files)
 
 
 def import_reference(ref):
@@ -103,8 +106,8 @@ def gen_shared(analysis, out, h=256, w=256, n=20, seed=0):
     xi = np.around(np.mgrid[-1:1:0.02, -1:1:0.02][1], decimals=2)[0]
     px = np.array([[0, 0], [17, 200], [128, 64], [255, 255]])
     grids = np.stack([analysis._interpolate_PTM(lu, lv, xi, I[:, y, x].astype(np.int32)) for y, x in px])
-    np.savez_compressed(os.path.join(out, f"ptm_shared_{h}x{w}_N{n}.npz"), lu=lu, lv=lv, I=I, coef=coef,
-                        grid_px=px, grid=grids, meta=meta())
+    golden_parts.save(os.path.join(out, f"ptm_shared_{h}x{w}_N{n}.npz"), lu=lu, lv=lv, I=I, coef=coef,
+                      grid_px=px, grid=grids, meta=meta())
 
 
 def gen_perpixel(analysis, out, roi=32, n=50, seed=1, roi_grid=4):
@@ -134,9 +137,9 @@ def gen_perpixel(analysis, out, roi=32, n=50, seed=1, roi_grid=4):
         tables = np.array(tables)
     finally:
         analysis.cst.ROI_DIAMETER = 400
-    np.savez_compressed(os.path.join(out, f"ptm_perpixel_{roi}x{roi}_N{n}.npz"), cams=cams, frames=frames,
-                        lx=lx, ly=ly, I=inten, coef=coef, grid=grid, tables=tables, roi_grid=roi_grid,
-                        meta=meta())
+    golden_parts.save(os.path.join(out, f"ptm_perpixel_{roi}x{roi}_N{n}.npz"), cams=cams, frames=frames,
+                      lx=lx, ly=ly, I=inten, coef=coef, grid=grid, tables=tables, roi_grid=roi_grid,
+                      meta=meta())
 
 
 def gen_edge(analysis, out, seed=2):
@@ -181,7 +184,7 @@ def gen_edge(analysis, out, seed=2):
             msgs[fname] = str(e)
     for k, v in msgs.items():
         arrays[f"msg_{k}"] = np.array(v)
-    np.savez_compressed(os.path.join(out, "ptm_edge.npz"), meta=meta(), **arrays)
+    golden_parts.save(os.path.join(out, "ptm_edge.npz"), meta=meta(), **arrays)
 
 
 def gen_rbf(analysis, out, n=20, npx=4, seed=3):
@@ -193,14 +196,14 @@ def gen_rbf(analysis, out, n=20, npx=4, seed=3):
     yi = np.around(yi, decimals=2)
     xi = np.around(xi, decimals=2)
     grids = np.stack([analysis._interpolate_RBF(lu, lv, xi, yi, I[p]) for p in range(npx)])
-    np.savez_compressed(os.path.join(out, f"rbf_shared_{npx}px_N{n}.npz"), lu=lu, lv=lv, I=I, grid=grids,
-                        meta=meta())
+    golden_parts.save(os.path.join(out, f"rbf_shared_{npx}px_N{n}.npz"), lu=lu, lv=lv, I=I, grid=grids,
+                      meta=meta())
 
 
 def gen_rbf_perpixel(analysis, out, roi=4, seed=5):
     """The reference's DEFAULT path: interpolate_intensities(interpolate_PTM=False) on per-pixel
     light vectors from compute_intensities, then prepare_images_data."""
-    p = np.load(os.path.join(out, "ptm_perpixel_32x32_N50.npz"))
+    p = golden_parts.load(os.path.join(out, "ptm_perpixel_32x32_N50.npz"))
     lx, ly, inten = p["lx"][:roi, :roi], p["ly"][:roi, :roi], p["I"][:roi, :roi]
     analysis.cst.ROI_DIAMETER = roi
     try:
@@ -220,9 +223,9 @@ def gen_rbf_perpixel(analysis, out, roi=4, seed=5):
         raised = type(e).__name__
     finally:
         analysis.cst.ROI_DIAMETER = 400
-    np.savez_compressed(os.path.join(out, f"rbf_perpixel_{roi}x{roi}_N{lx.shape[-1]}.npz"), lx=lx, ly=ly, I=inten,
-                        grid=grid, tables=tables, singular_lx=lx2, singular_ly=ly2, singular_raises=np.array(raised),
-                        meta=meta())
+    golden_parts.save(os.path.join(out, f"rbf_perpixel_{roi}x{roi}_N{lx.shape[-1]}.npz"), lx=lx, ly=ly, I=inten,
+                      grid=grid, tables=tables, singular_lx=lx2, singular_ly=ly2, singular_raises=np.array(raised),
+                      meta=meta())
 
 
 def gen_lookup(utilities, out, seed=4):
@@ -235,8 +238,8 @@ def gen_lookup(utilities, out, seed=4):
         for x, y in zip(xs, ys):
             lx, ly = utilities.draw_light_roi_position(int(x), int(y), (h, w), to_light_vector=True)
             rows.append((x, y, h, w, lx, ly, round((1 + lx) / 2 * 100), round((1 + ly) / 2 * 100)))
-    np.savez_compressed(os.path.join(out, "relight_lookup.npz"), rows=np.array(rows, dtype=np.float64),
-                        meta=meta())
+    golden_parts.save(os.path.join(out, "relight_lookup.npz"), rows=np.array(rows, dtype=np.float64),
+                      meta=meta())
 
 
 def main():

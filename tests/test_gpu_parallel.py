@@ -71,7 +71,7 @@ def test_rowtiled_fit_two_ranks_one_gpu(cuda):
                                               (2, "64x96", ["--weak"]), (2, "96x128", ["--stack", "pixel"]),
                                               (3, "48x64", ["--config", "c4"])])
 def test_bench_multi_rank_end_to_end_parity(cuda, gpus, shape, extra):
-    """bench.py --gpus N (ranks sharing cuda:0 over gloo): the strong-scaling line, the all-gather legs and
+    """bench.py --full --gpus N (ranks sharing cuda:0 over gloo): the strong-scaling line, the all-gather legs and
     the overlapped row-chunked fit whose gathered map (block-cyclic rows generated per rank) rank 0 checks
     block by block against the oracle (e2e_parity) — on the same kernel family as the 1-GPU line: 8-bit
     stacks on the h16 fit, the reference's pixel-major stack, and all three HSH-16 channels of c4."""
@@ -82,7 +82,7 @@ def test_bench_multi_rank_end_to_end_parity(cuda, gpus, shape, extra):
     env = dict(os.environ)
     env.pop("WORLD_SIZE", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--dist-backend", "gloo",
-                        "--config", "c2", "--shape", shape, "--steps", "2", "--warmup", "1", "--no-cpu"] + extra,
+                        "--config", "c2", "--shape", shape, "--steps", "2", "--warmup", "1", "--full", "--no-cpu"] + extra,
                        capture_output=True, text=True, timeout=240, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -19,10 +19,10 @@ run() {  # name seconds cmd...
 for c in ${CONFIGS:-c3 c2 c4 c10 c5 c9 c6 c7 c8 c8n200}; do
   budget=8; [ $c = c3 ] && budget=16; extra=""; case $c in c8n200) extra="--no-cpu";; esac
   run bench_$c$SUFFIX 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_$c$SUFFIX -o run -- \
-      python3 bench.py --config $c --cpu-budget $budget $extra $BENCH_ARGS
+      python3 bench.py --full --config $c --cpu-budget $budget $extra $BENCH_ARGS
 done
 if [ -z "$SKIP_EXTRA" ]; then
-  run bench_c5_hot 200 python3 bench.py --config c5 --map-sets 1 --no-cpu
-  run bench_c9_hot 200 python3 bench.py --config c9 --map-sets 1 --no-cpu
+  run bench_c5_hot 200 python3 bench.py --full --config c5 --map-sets 1 --no-cpu
+  run bench_c9_hot 200 python3 bench.py --full --config c9 --map-sets 1 --no-cpu
 fi
 exit 0
