@@ -262,6 +262,43 @@ int rti_fit_shared_residual_svd(const double* U, const double* W, int k, int N, 
                                 float* coef, int coef_layout, int64_t coef_channel_stride,
                                 float* res, double* partial, int kernel, rti_stream_t stream);
 
+/* ---- device: robust shared-direction fit (rti_fit_robust.hip) --------------------------
+ * The least squares of analysis.py:280-298 with the samples the model cannot describe left out: an
+ * intensity window (clipped highlights at 255, self-shadow at 0 in the reference's 8-bit V channel) and,
+ * with iters > 0, Huber-weighted IRLS.  Per channel c and pixel p, with a_n the rows of A and
+ * y_n = I[c][n][p] in fp64:
+ *   window    win_n = (lo <= y_n <= hi), compared on the input value; m = Σ win_n (±inf = no bound)
+ *   solve(w)  G = Σ w_n a_n a_nᵀ, b = Σ w_n a_n y_n in fp64, Cholesky of G; the solve FAILS at a pivot
+ *             d_j <= 1e-10·max_i G_ii, else coef = G⁻¹ b
+ *   fallback  if m < min_lights or solve(win) fails the pixel uses every light (win_n = 1, m = N,
+ *             coef = solve(1)) and *fallback_px is incremented; if that fails too coef and res are NaN
+ *             (as rti_fit_perpixel_cam for a singular light set with rcond >= 0)
+ *   IRLS      for t = 1..iters: r_n = y_n − a_n·coef, w_n = win_n·(|r_n| <= delta ? 1 : delta/|r_n|)
+ *             (delta in intensity units), coef = solve(w); a failed solve keeps the previous coef and
+ *             ends that pixel's iteration
+ *   coef      fp32, coef_layout / coef_channel_stride as rti_fit_shared
+ *   res[c][p]  = sqrt(Σ win_n r_n² / m), r from the final coef; fp32 [C][P], may be NULL
+ *   kept[c][p] = m (N on fallback pixels); int32 [C][P], may be NULL
+ * A: device fp64 design matrix [N][k] (rti_design_matrix).  I, in_dtype (F32 / U8 / I32), P, C and the
+ * strides as rti_fit_shared (light-major).  fallback_px: NULL or a device int the caller zeroes.
+ * k ∈ {6, 9}; k = 16 returns RTI_ERR_UNSUPPORTED: one lane owns one pixel, and 136 + 16 fp64
+ * accumulators do not fit a lane's registers (splitting a pixel over lanes is future work).
+ * RTI_ERR_BAD_ARG: null A / I / coef, N < k, lo > hi or a NaN bound, min_lights outside [k, N], iters
+ * outside [0, 16], delta <= 0 with iters > 0, or any kernel bit but RTI_KERNEL_ONE_LAUNCH.
+ * Forms (the same arithmetic in the same order): RESIDENT (AUTO when iters > 0 and a tile fits) copies a
+ * workgroup's tile [N][TP] of the stack into LDS once and runs the window pass and every IRLS pass from
+ * there, so the stack is read from HBM once whatever iters is; TP = the largest of 256 / 128 / 64 pixels
+ * with N·TP·sizeof(element) <= 160 KiB.  STREAMING (no tile fits, iters == 0, or kernel =
+ * RTI_KERNEL_ONE_LAUNCH, for measurement and tests) reads the stack from global memory in every pass:
+ * once for iters == 0, iters + 2 times otherwise.  rti_fit_shared_robust_plan returns 0 for the
+ * streaming form, else the resident tile's pixel count TP. */
+int rti_fit_shared_robust(const double* A, int k, int N, const void* I, int in_dtype, int64_t P, int C,
+                          int64_t light_stride, int64_t channel_stride,
+                          float lo, float hi, int min_lights, int iters, float delta,
+                          float* coef, int coef_layout, int64_t coef_channel_stride,
+                          float* res, int32_t* kept, int* fallback_px, int kernel, rti_stream_t stream);
+int rti_fit_shared_robust_plan(int k, int N, int in_dtype, int iters, int kernel);
+
 /* ---- device: per-pixel PTM fit, light vectors generated in-kernel ------------------
  * Fuses compute_intensities' light vectors (analysis.py:221-231) into the
  * per-pixel PTM solve (analysis.py:280-298): for pixel (x, y) of an H×W stack

@@ -1,0 +1,404 @@
+// rti_fit_robust.hip -- robust shared-direction fit: intensity window + Huber IRLS (gfx950).
+//
+// The plain least squares of analysis.py:280-298 treats every one of a pixel's N samples alike.  On the
+// 8-bit V channel of a metal surface (FeatureMatcher.py:183-184, analysis.py:219) many of them are clipped
+// at 255 (specular highlight) or sit at 0 (self-shadow); the PTM/HSH model cannot describe those.  Here each
+// pixel drops the samples outside [lo, hi] and, optionally, reweights the rest by Huber's function of their
+// residuals.  Per channel and pixel, with A the shared fp64 design [N][k] and y_n the pixel's samples:
+//
+//   window    win_n = lo <= y_n <= hi, m = Σ win_n
+//   solve(w)  G = Σ w_n a_n a_nᵀ, b = Σ w_n a_n y_n (fp64), Cholesky G = L Lᵀ; fails at a pivot
+//             d_j <= 1e-10·max_i G_ii, else coef = G⁻¹ b
+//   fallback  m < min_lights or solve(win) failed: win = 1, m = N, coef = solve(1) (NaN if that fails too);
+//             the pixel is counted in *fallback_px
+//   IRLS      iters times: r_n = y_n − a_n·coef, w_n = win_n·min(1, delta/|r_n|), coef = solve(w); a failed
+//             solve keeps the previous coef and ends the pixel's iteration
+//   outputs   coef (fp32), res = sqrt(Σ win_n r_n² / m), kept = m
+//
+// The weights depend on the pixel's own residuals, so there is no shared operator: every pass accumulates a
+// k×k Gram per pixel.  One lane owns one pixel; the rows of A are wave-uniform (scalar loads) and the fp64
+// state is k(k+1)/2 + k accumulators (54 VGPRs at k = 6, 108 at k = 9), factored in registers like
+// rti_perpixel.hip's ne_solve.
+//
+// Two forms run the same arithmetic in the same order:
+//   resident   a workgroup of TP lanes copies its tile [N][TP] of the stack, in the input dtype, into LDS once
+//              (16-byte loads when the planes are 16-byte aligned) and every pass reads the samples from there:
+//              one stack read from HBM whatever iters is.  TP = the largest of 256 / 128 / 64 pixels whose tile
+//              fits the CU's 160 KiB (rti_fit_shared_robust_plan); the kernel stages nothing else.
+//   streaming  every pass reads the samples from global memory (no tile fits, iters == 0, or forced).
+// With iters == 0 the residual energy comes from the same pass as the solve, Σ w r² = q − 2 cᵀb + cᵀG c with
+// q = Σ w y² (fp64: the cancellation leaves ~1e-9 of q), so that fit reads the stack once; with iters > 0 a last
+// pass forms the residuals of the final coefficients explicitly.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "rti_internal.h"
+
+namespace rti {
+namespace {
+
+typedef uint32_t uintx4 __attribute__((ext_vector_type(4)));
+
+constexpr int64_t RB_LDS_BYTES = 160 * 1024;  // LDS of one CU
+constexpr double RB_PIVOT_TOL = 1e-10;        // a pivot <= RB_PIVOT_TOL·max diag G fails the solve
+
+template <int K>
+__host__ __device__ constexpr int rb_tri(int i, int j) {  // packed lower triangle, i >= j
+  return i * (i + 1) / 2 + j;
+}
+
+template <int K>
+struct RbSys {
+  double g[K * (K + 1) / 2], b[K], q;
+  int m;
+};
+
+// The samples of one pixel: lane-private address, `step` elements between lights (LDS tile or global plane).
+template <typename T>
+struct RbSamples {
+  const T* p;
+  int64_t step;
+  __device__ __forceinline__ double operator()(int n) const { return (double)p[(int64_t)n * step]; }
+};
+
+enum { RB_W_WINDOW = 0, RB_W_ALL = 1, RB_W_HUBER = 2 };
+
+// sample weight: the window (or 1 for every light on a fallback pixel) times Huber's weight of the residual
+template <int K, int MODE>
+__device__ __forceinline__ double rb_weight(const double* __restrict__ An, double y, double lo, double hi, bool all,
+                                            const double (&c)[K], double delta) {
+  const double win = (all || (y >= lo && y <= hi)) ? 1.0 : 0.0;
+  if constexpr (MODE == RB_W_ALL) return 1.0;
+  if constexpr (MODE == RB_W_WINDOW) return win;
+  double r = y;
+#pragma unroll
+  for (int i = 0; i < K; ++i) r = fma(-An[i], c[i], r);
+  const double ar = fabs(r);
+  return win * (ar <= delta ? 1.0 : delta / ar);
+}
+
+// one pass over the pixel's N samples: G, b, q and the count of samples in the window
+template <int K, int MODE, bool NEED_Q, typename S>
+__device__ __forceinline__ void rb_accumulate(const double* __restrict__ A, int N, const S& y_of, double lo, double hi,
+                                              bool all, const double (&c)[K], double delta, RbSys<K>& s) {
+#pragma unroll
+  for (int i = 0; i < K * (K + 1) / 2; ++i) s.g[i] = 0.0;
+#pragma unroll
+  for (int i = 0; i < K; ++i) s.b[i] = 0.0;
+  s.q = 0.0;
+  int m = 0;
+#pragma unroll 2
+  for (int n = 0; n < N; ++n) {
+    const double* An = A + (int64_t)n * K;  // wave-uniform row -> SGPR pairs
+    const double y = y_of(n);
+    const double w = rb_weight<K, MODE>(An, y, lo, hi, all, c, delta);
+    if constexpr (MODE == RB_W_WINDOW) m += w != 0.0 ? 1 : 0;
+    const double wy = w * y;
+    if constexpr (NEED_Q) s.q = fma(wy, y, s.q);
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      const double wa = w * An[i];
+#pragma unroll
+      for (int j = 0; j <= i; ++j) s.g[rb_tri<K>(i, j)] = fma(wa, An[j], s.g[rb_tri<K>(i, j)]);
+      s.b[i] = fma(An[i], wy, s.b[i]);
+    }
+  }
+  s.m = MODE == RB_W_WINDOW ? m : N;
+}
+
+// Cholesky solve of G c = b in registers (the idiom of rti_perpixel.hip's ne_solve).  Returns false, leaving c
+// untouched, when a pivot is not above RB_PIVOT_TOL·max diag G (NaN included).
+template <int K>
+__device__ __forceinline__ bool rb_solve(const RbSys<K>& s, double (&c)[K]) {
+  double L[K * (K + 1) / 2];
+  double dmax = 0.0;
+#pragma unroll
+  for (int i = 0; i < K; ++i) dmax = fmax(dmax, s.g[rb_tri<K>(i, i)]);
+  const double thr = RB_PIVOT_TOL * dmax;
+  bool ok = true;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    double d = s.g[rb_tri<K>(j, j)];
+#pragma unroll
+    for (int p = 0; p < j; ++p) d = fma(-L[rb_tri<K>(j, p)], L[rb_tri<K>(j, p)], d);
+    ok = ok && (d > thr);
+    const double ljj = sqrt(d > 0.0 ? d : 1.0);
+    const double inv = 1.0 / ljj;
+    L[rb_tri<K>(j, j)] = inv;  // the diagonal is kept inverted
+#pragma unroll
+    for (int i = j + 1; i < K; ++i) {
+      double t = s.g[rb_tri<K>(i, j)];
+#pragma unroll
+      for (int p = 0; p < j; ++p) t = fma(-L[rb_tri<K>(i, p)], L[rb_tri<K>(j, p)], t);
+      L[rb_tri<K>(i, j)] = t * inv;
+    }
+  }
+  double z[K], x[K];
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    double t = s.b[i];
+#pragma unroll
+    for (int p = 0; p < i; ++p) t = fma(-L[rb_tri<K>(i, p)], z[p], t);
+    z[i] = t * L[rb_tri<K>(i, i)];
+  }
+#pragma unroll
+  for (int i = K - 1; i >= 0; --i) {
+    double t = z[i];
+#pragma unroll
+    for (int p = i + 1; p < K; ++p) t = fma(-L[rb_tri<K>(p, i)], x[p], t);
+    x[i] = t * L[rb_tri<K>(i, i)];
+  }
+  if (ok) {
+#pragma unroll
+    for (int i = 0; i < K; ++i) c[i] = x[i];
+  }
+  return ok;
+}
+
+struct RbOut {
+  double ss;  // Σ win r²
+  int m;
+  bool fell;
+};
+
+// The whole fit of one pixel from its samples (either form).  ITER: iters > 0.
+template <int K, bool ITER, typename S>
+__device__ __forceinline__ RbOut rb_pixel(const double* __restrict__ A, int N, const S& y_of, double lo, double hi,
+                                          int min_lights, int iters, double delta, double (&c)[K]) {
+  RbSys<K> s;
+#pragma unroll
+  for (int i = 0; i < K; ++i) c[i] = __builtin_nan("");
+  rb_accumulate<K, RB_W_WINDOW, !ITER>(A, N, y_of, lo, hi, false, c, delta, s);
+  RbOut o;
+  o.m = s.m;
+  bool ok = s.m >= min_lights && rb_solve<K>(s, c);
+  o.fell = !ok;
+  if (!ok) {  // every light; a second failure leaves the NaN
+    rb_accumulate<K, RB_W_ALL, !ITER>(A, N, y_of, lo, hi, true, c, delta, s);
+    o.m = N;
+    ok = rb_solve<K>(s, c);
+  }
+  if constexpr (!ITER) {
+    // Σ w r² = q − 2 cᵀb + cᵀG c with this pass's own G, b, q (w ∈ {0, 1})
+    double e = s.q;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      double gc = 0.0;
+#pragma unroll
+      for (int j = 0; j < K; ++j) gc = fma(s.g[i >= j ? rb_tri<K>(i, j) : rb_tri<K>(j, i)], c[j], gc);
+      e = fma(c[i], gc - 2.0 * s.b[i], e);
+    }
+    o.ss = e < 0.0 ? 0.0 : e;  // rounding can leave an exact fit below zero; NaN passes
+  } else {
+    for (int t = 0; t < iters && ok; ++t) {
+      rb_accumulate<K, RB_W_HUBER, false>(A, N, y_of, lo, hi, o.fell, c, delta, s);
+      ok = rb_solve<K>(s, c);  // a failed solve keeps the previous coefficients and stops
+    }
+    double e = 0.0;
+#pragma unroll 2
+    for (int n = 0; n < N; ++n) {
+      const double* An = A + (int64_t)n * K;
+      const double y = y_of(n);
+      double r = y;
+#pragma unroll
+      for (int i = 0; i < K; ++i) r = fma(-An[i], c[i], r);
+      const bool in = o.fell || (y >= lo && y <= hi);
+      e = fma(in ? r : 0.0, r, e);
+    }
+    o.ss = e;
+  }
+  return o;
+}
+
+// TP lanes per workgroup, one pixel each.  RESIDENT: the tile [N][TP] is copied into LDS first (vec: by 16-byte
+// loads; the host passes vec only when every plane of every tile is 16-byte aligned) and the passes read it from
+// there.  A lane past P reads pixel P − 1 and stores nothing.
+template <int K, typename T, int TP, bool RESIDENT, bool ITER, int LAYOUT>
+__global__ void __launch_bounds__(TP)
+fit_robust_k(const double* __restrict__ A, int N, const T* __restrict__ I, int64_t P, int64_t lstride, int64_t cstride,
+             double lo, double hi, int min_lights, int iters, double delta, float* __restrict__ coef, int64_t ocstride,
+             float* __restrict__ res, int32_t* __restrict__ kept, int* __restrict__ fallback_px, int vec) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char rb_lds[];
+  const int t = threadIdx.x;
+  const int64_t tile0 = (int64_t)blockIdx.x * TP;
+  const int64_t p = tile0 + t;
+  const bool live = p < P;
+  const int64_t pr = live ? p : P - 1;
+  const T* __restrict__ src = I + (int64_t)blockIdx.y * cstride;
+
+  RbSamples<T> y_of;
+  if constexpr (RESIDENT) {
+    T* tile = reinterpret_cast<T*>(rb_lds);
+    if (vec && tile0 + TP <= P) {  // workgroup-uniform
+      constexpr int VR = TP * (int)sizeof(T) / 16;  // 16-byte vectors per plane row
+      constexpr int EV = 16 / (int)sizeof(T);       // elements per vector
+      uintx4* tv = reinterpret_cast<uintx4*>(rb_lds);
+      const int total = N * VR;
+#pragma unroll 4
+      for (int idx = t; idx < total; idx += TP) {
+        const int n = idx / VR, v = idx - n * VR;
+        tv[idx] = __builtin_nontemporal_load(reinterpret_cast<const uintx4*>(src + (int64_t)n * lstride + tile0 + v * EV));
+      }
+    } else {
+#pragma unroll 4
+      for (int n = 0; n < N; ++n) tile[n * TP + t] = __builtin_nontemporal_load(src + (int64_t)n * lstride + pr);
+    }
+    __syncthreads();
+    y_of.p = tile + t;
+    y_of.step = TP;
+  } else {
+    y_of.p = src + pr;
+    y_of.step = lstride;
+  }
+
+  double c[K];
+  const RbOut o = rb_pixel<K, ITER>(A, N, y_of, lo, hi, min_lights, iters, delta, c);
+
+  if (live) {
+    float* __restrict__ dst = coef + (int64_t)blockIdx.y * ocstride;
+#pragma unroll
+    for (int i = 0; i < K; ++i) {
+      if constexpr (LAYOUT == RTI_COEF_PLANAR)
+        dst[(int64_t)i * P + p] = (float)c[i];
+      else
+        dst[p * K + i] = (float)c[i];
+    }
+    if (res) res[(int64_t)blockIdx.y * P + p] = (float)sqrt(o.ss / (double)o.m);
+    if (kept) kept[(int64_t)blockIdx.y * P + p] = o.m;
+  }
+  if (fallback_px) {  // one atomic per wave that has any
+    const unsigned long long fb = __ballot(live && o.fell);
+    if (fb != 0 && (t & 63) == 0) atomicAdd(fallback_px, __popcll(fb));
+  }
+}
+
+struct RbArgs {
+  const double* A;
+  int k, N;
+  const void* I;
+  int in_dtype;
+  int64_t P, lstride, cstride;
+  int C;
+  double lo, hi;
+  int min_lights, iters;
+  double delta;
+  float* coef;
+  int layout;
+  int64_t ocstride;
+  float* res;
+  int32_t* kept;
+  int* fallback_px;
+  int tp;  // resident tile pixels, 0 = streaming
+  int vec;
+  hipStream_t s;
+};
+
+template <int K, typename T, int TP, bool RESIDENT, bool ITER, int LAYOUT>
+int launch_rb(const RbArgs& a) {
+  auto kern = fit_robust_k<K, T, TP, RESIDENT, ITER, LAYOUT>;
+  const size_t lds = RESIDENT ? (size_t)a.N * TP * sizeof(T) : 0;
+  if (lds > 64 * 1024 && reserve_lds(reinterpret_cast<const void*>(kern), lds) != hipSuccess)
+    return fail(RTI_ERR_HIP, "rti_fit_shared_robust: cannot reserve %zu bytes of LDS", lds);
+  const dim3 grid(grid_1d(a.P, TP), a.C);
+  hipLaunchKernelGGL(kern, grid, dim3(TP), lds, a.s, a.A, a.N, static_cast<const T*>(a.I), a.P, a.lstride, a.cstride,
+                     a.lo, a.hi, a.min_lights, a.iters, a.delta, a.coef, a.ocstride, a.res, a.kept, a.fallback_px, a.vec);
+  return check_launch("rti_fit_shared_robust");
+}
+
+template <int K, typename T, int LAYOUT>
+int launch_rb_form(const RbArgs& a) {
+  // the resident form runs only with iters > 0 (rti_fit_shared_robust_plan)
+  switch (a.tp) {
+    case 256: return launch_rb<K, T, 256, true, true, LAYOUT>(a);
+    case 128: return launch_rb<K, T, 128, true, true, LAYOUT>(a);
+    case 64: return launch_rb<K, T, 64, true, true, LAYOUT>(a);
+    default:
+      return a.iters > 0 ? launch_rb<K, T, 256, false, true, LAYOUT>(a) : launch_rb<K, T, 256, false, false, LAYOUT>(a);
+  }
+}
+
+template <int K, typename T>
+int launch_rb_l(const RbArgs& a) {
+  return a.layout == RTI_COEF_PLANAR ? launch_rb_form<K, T, RTI_COEF_PLANAR>(a)
+                                     : launch_rb_form<K, T, RTI_COEF_PIXEL_MAJOR>(a);
+}
+
+template <typename T>
+int launch_rb_k(const RbArgs& a) {
+  return a.k == 6 ? launch_rb_l<6, T>(a) : launch_rb_l<9, T>(a);
+}
+
+int rb_elem_size(int in_dtype) { return in_dtype == RTI_U8 ? 1 : 4; }
+
+}  // namespace
+}  // namespace rti
+
+using namespace rti;
+
+extern "C" int rti_fit_shared_robust_plan(int k, int N, int in_dtype, int iters, int kernel) {
+  if ((k != 6 && k != 9) || N < k || iters <= 0 || (kernel & RTI_KERNEL_ONE_LAUNCH)) return 0;
+  if (in_dtype != RTI_F32 && in_dtype != RTI_U8 && in_dtype != RTI_I32) return 0;
+  for (int tp : {256, 128, 64})
+    if ((int64_t)N * tp * rb_elem_size(in_dtype) <= RB_LDS_BYTES) return tp;
+  return 0;
+}
+
+extern "C" int rti_fit_shared_robust(const double* A, int k, int N, const void* I, int in_dtype, int64_t P, int C,
+                                     int64_t light_stride, int64_t channel_stride, float lo, float hi,
+                                     int min_lights, int iters, float delta, float* coef, int coef_layout,
+                                     int64_t coef_channel_stride, float* res, int32_t* kept, int* fallback_px,
+                                     int kernel, rti_stream_t stream) {
+  if (!kernel_bits_ok(kernel, RTI_KERNEL_AUTO, RTI_KERNEL_ONE_LAUNCH))
+    return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: unknown kernel bits 0x%x", kernel);
+  if (!A || !I || !coef) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: null pointer");
+  if (N <= 0 || P <= 0 || C <= 0 || C > 65535) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: bad N/P/C");
+  if (k == 16)
+    return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_robust: k=16 (its 136 + 16 fp64 accumulators do not fit one lane)");
+  if (k != 6 && k != 9) return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_robust: k=%d (supported: 6, 9)", k);
+  if (in_dtype != RTI_F32 && in_dtype != RTI_U8 && in_dtype != RTI_I32)
+    return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_robust: input dtype %d", in_dtype);
+  if (N < k) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: N=%d < k=%d", N, k);
+  if (!(lo <= hi)) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: window needs lo <= hi, neither NaN");
+  if (min_lights < k || min_lights > N)
+    return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: min_lights=%d outside [k=%d, N=%d]", min_lights, k, N);
+  if (iters < 0 || iters > 16) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: iters=%d outside [0, 16]", iters);
+  if (iters > 0 && !(delta > 0.0f)) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: delta must be > 0");
+  if (coef_layout != RTI_COEF_PIXEL_MAJOR && coef_layout != RTI_COEF_PLANAR)
+    return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: coef layout %d", coef_layout);
+  RbArgs a;
+  a.A = A;
+  a.k = k;
+  a.N = N;
+  a.I = I;
+  a.in_dtype = in_dtype;
+  a.P = P;
+  a.C = C;
+  a.lstride = light_stride ? light_stride : P;
+  a.cstride = channel_stride ? channel_stride : (int64_t)N * a.lstride;
+  a.lo = (double)lo;
+  a.hi = (double)hi;
+  a.min_lights = min_lights;
+  a.iters = iters;
+  a.delta = (double)delta;
+  a.coef = coef;
+  a.layout = coef_layout;
+  a.ocstride = coef_channel_stride ? coef_channel_stride : P * k;
+  a.res = res;
+  a.kept = kept;
+  a.fallback_px = fallback_px;
+  a.s = (hipStream_t)stream;
+  if (a.lstride < P) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: light_stride < P");
+  if (C > 1 && a.cstride < (int64_t)N * a.lstride) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: channel_stride");
+  if (C > 1 && a.ocstride < P * k) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: coef_channel_stride");
+  a.tp = rti_fit_shared_robust_plan(k, N, in_dtype, iters, kernel);
+  const int64_t es = rb_elem_size(in_dtype);
+  a.vec = aligned_to(I, 16) && a.lstride * es % 16 == 0 && a.cstride * es % 16 == 0;
+  note_launches(1);
+  switch (in_dtype) {
+    case RTI_F32: return launch_rb_k<float>(a);
+    case RTI_U8: return launch_rb_k<uint8_t>(a);
+    default: return launch_rb_k<int32_t>(a);
+  }
+}

@@ -4,6 +4,7 @@ bara96/Smartphone-based-RTI: analysis.py:196-411, interactive_relighting.py:11-3
     import rti
     coef = rti.fit(I, lu, lv, basis="ptm")          # I: CUDA [N, H, W]
     img = rti.relight(coef, 0.3, -0.2)               # [H, W]
+    coef, res, kept = rti.fit_robust(I, lu, lv, lo=1, hi=254, iters=3, delta=5.0)  # clipped samples left out
 
 Compute runs in HIP kernels of librti.so (include/rti.h); importing this
 package does not touch the GPU.
@@ -11,12 +12,14 @@ package does not touch the GPU.
 from . import _lib
 from ._lib import RTIError, RTILibraryMissing
 from .api import (BASES, apply_operator, basis_eval, basis_id, basis_operator, basis_terms, design_matrix, fit,
-                  fit_residual, fit_shared_into, fit_shared_residual_into, fit_with_residual, gram_inverse,
+                  fit_residual, fit_robust, fit_robust_into, fit_shared_into, fit_shared_residual_into, fit_with_residual,
+                  gram_inverse,
                   interpolate_rbf, interpolate_rbf_perpixel, light_dirs, lsq_factors, pinv, q8_operator, h16_operator, rbf_operator,
                   relight, relight_frame)
 
 __all__ = ["BASES", "RTIError", "RTILibraryMissing", "apply_operator", "basis_eval", "basis_id", "basis_operator",
-           "basis_terms", "design_matrix", "fit", "fit_residual", "fit_shared_into", "fit_shared_residual_into",
+           "basis_terms", "design_matrix", "fit", "fit_residual", "fit_robust", "fit_robust_into", "fit_shared_into",
+           "fit_shared_residual_into",
            "fit_with_residual", "gram_inverse", "interpolate_rbf", "interpolate_rbf_perpixel", "light_dirs",
            "lsq_factors", "pinv", "q8_operator", "h16_operator",
            "rbf_operator", "relight", "relight_frame", "library_path", "load"]

@@ -112,6 +112,10 @@ SIGNATURES = {
     "rti_fit_shared_residual_svd": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_i64,
                                              _c_int, _c_i64, _c_i64, _c_void_p, _c_int, _c_i64, _c_void_p, _c_void_p,
                                              _c_int, _c_void_p]),
+    "rti_fit_shared_robust": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_i64, _c_int, _c_i64, _c_i64,
+                                       ctypes.c_float, ctypes.c_float, _c_int, _c_int, ctypes.c_float, _c_void_p,
+                                       _c_int, _c_i64, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p]),
+    "rti_fit_shared_robust_plan": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
     "rti_fit_perpixel_cam": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_i64, _c_double,
                                       _c_double, _c_double, _c_void_p, _c_int, _c_int, _c_void_p]),
     "rti_fit_perpixel_dirs": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_i64, _c_double,

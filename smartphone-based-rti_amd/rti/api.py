@@ -560,6 +560,74 @@ def fit_with_residual(I, lu, lv, basis="ptm", rcond=None, *, layout="pixel", chu
     return (coef, res, rms) if I.dim() == 4 else (coef[0], res[0], rms[0])
 
 
+def fit_robust_into(A_dev, I3, coef, res, kept, fallback, *, k, lo, hi, min_lights, iters=0, delta=0.0,
+                    layout="pixel", kernel=0):
+    """Launch ``rti_fit_shared_robust`` on preallocated tensors (no allocation, graph-capturable).
+
+    A_dev fp64 [N, k] (``design_matrix`` on the device), I3 CUDA [C, N, P] light-major (fp32/u8/int32), coef
+    fp32 [C, P, k] / [C, k, P], res fp32 [C, P] or None, kept int32 [C, P] or None, fallback int32 [1] zeroed
+    (or None): the count of pixels that fell back to every light.  lo / hi: the intensity window (±inf = no
+    bound); kernel: 0 or ``RTI_KERNEL_ONE_LAUNCH`` (the streaming form, for measurement)."""
+    C, N, P = I3.shape
+    st = L.lib().rti_fit_shared_robust(_vp(A_dev), k, N, _vp(I3), _IN_DTYPES[I3.dtype], P, C, P, N * P, float(lo),
+                                       float(hi), int(min_lights), int(iters), float(delta), _vp(coef),
+                                       _layout_id(layout), P * k, None if res is None else _vp(res),
+                                       None if kept is None else _vp(kept),
+                                       None if fallback is None else _vp(fallback), int(kernel), _stream_of(I3))
+    L.check(st, "rti_fit_shared_robust")
+
+
+def _robust_window(I, lo, hi):
+    """fit_robust's default window: none, except 1..254 for a uint8 stack given neither bound."""
+    if lo is None and hi is None and I.dtype == torch.uint8:
+        return 1.0, 254.0
+    return (-np.inf if lo is None else float(lo)), (np.inf if hi is None else float(hi))
+
+
+def fit_robust(I, lu, lv, basis="ptm", *, lo=None, hi=None, min_lights=None, iters=0, delta=None, layout="pixel",
+               stats=None, kernel=0):
+    """Shared-direction fit that leaves out the samples the model cannot describe
+    (``rti_fit_shared_robust``): per pixel, the samples outside the intensity window [lo, hi] (clipped
+    highlights, self-shadow) are dropped and, with iters > 0, the rest are reweighted ``iters`` times by
+    Huber's function of their residuals, w = min(1, delta/|r|) (delta in intensity units).
+
+    I: CUDA [N, P], [N, H, W] or [C, N, H, W] (light-major, fp32/u8/int32); PTM-6 or HSH-9.  lo / hi:
+    None = no bound; a uint8 stack given NEITHER bound uses lo = 1, hi = 254 (the 8-bit clip values are
+    dropped).  min_lights (default k): a pixel with fewer samples in the window, or whose windowed system
+    is rank-deficient, falls back to every light.  Returns ``(coef, res, kept)``: coef fp32 as ``fit``
+    returns it (layout), res fp32 with I's spatial shape (leading C for 4-D stacks) = the RMS residual
+    over the pixel's window, kept int32 of the same shape = the samples in its window (N on fallback
+    pixels).  ``stats``, if a dict, receives ``fallback_px`` (this waits for the kernel)."""
+    _require_cuda(I, "I")
+    if I.dtype not in _IN_DTYPES:
+        raise ValueError(f"I dtype {I.dtype} unsupported (float32, uint8 or int32)")
+    cl = _layout_id(layout)
+    b = basis_id(basis)
+    k = basis_terms(b)
+    C, N, P, spatial = _stack_shape(I)
+    if N < k:
+        raise ValueError(f"shapes not aligned: {N} lights < {k} basis terms (analysis.py:298)")
+    A = design_matrix(lu, lv, b)
+    if A.shape[0] != N:
+        raise ValueError(f"{A.shape[0]} light directions for {N} intensity planes")
+    lo, hi = _robust_window(I, lo, hi)
+    dev = I.device
+    A_dev = torch.as_tensor(A, device=dev).contiguous()
+    Ic = I.contiguous().reshape(C, N, P)
+    coef = torch.empty((C, P, k) if cl == L.RTI_COEF_PIXEL_MAJOR else (C, k, P), dtype=torch.float32, device=dev)
+    res = torch.empty((C, P), dtype=torch.float32, device=dev)
+    kept = torch.empty((C, P), dtype=torch.int32, device=dev)
+    fallback = torch.zeros(1, dtype=torch.int32, device=dev)
+    fit_robust_into(A_dev, Ic, coef, res, kept, fallback, k=k, lo=lo, hi=hi,
+                    min_lights=k if min_lights is None else min_lights, iters=iters,
+                    delta=0.0 if delta is None else delta, layout=cl, kernel=kernel)
+    if isinstance(stats, dict):
+        stats["fallback_px"] = int(fallback.item())
+    coef = coef.reshape((C,) + spatial + (k,)) if cl == L.RTI_COEF_PIXEL_MAJOR else coef.reshape((C, k) + spatial)
+    res, kept = res.reshape((C,) + spatial), kept.reshape((C,) + spatial)
+    return (coef, res, kept) if I.dim() == 4 else (coef[0], res[0], kept[0])
+
+
 def light_dirs(cams, H, W, origin=(0.0, 0.0), device="cuda"):
     """compute_intensities' light vectors on the GPU: (lu, lv) fp32 [H, W, N]."""
     cams_d = torch.as_tensor(np.asarray(cams.detach().cpu() if torch.is_tensor(cams) else cams, np.float64),

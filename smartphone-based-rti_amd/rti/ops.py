@@ -1,5 +1,5 @@
 """PyTorch custom ops over the C ABI: ``torch.ops.rti.fit_shared`` / ``fit_shared_residual`` /
-``fit_residual`` / ``relight``.
+``fit_robust`` / ``fit_residual`` / ``relight``.
 
 They let the fit and relight kernels sit inside torch programs (and
 ``torch.library`` fake-tensor tracing) while the compute stays in librti's
@@ -100,6 +100,47 @@ def _(U, W, I, planar=False, chunks=0):
     return (I.new_empty(lead + ((k, P) if planar else (P, k)), dtype=torch.float32),
             I.new_empty(lead + (P,), dtype=torch.float32),
             I.new_empty(lead + (nb,), dtype=torch.float64))
+
+
+@torch.library.custom_op("rti::fit_robust", mutates_args=())
+def fit_robust(A: torch.Tensor, I: torch.Tensor, lo: float, hi: float, min_lights: int, iters: int = 0,
+               delta: float = 0.0, planar: bool = False,
+               kernel: int = 0) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The robust shared fit (``rti_fit_shared_robust``: intensity window [lo, hi], ±inf = no bound, and
+    ``iters`` Huber IRLS steps of width delta).  A fp64 CUDA [N, k] (``rti.design_matrix``), I CUDA [N, P] or
+    [C, N, P] (fp32/u8/int32) -> ``(coef, res, kept, fallback_px)``: coef fp32 [C?, P, k] (or [C?, k, P] if
+    planar), res fp32 [C?, P], kept int32 [C?, P], fallback_px int32 [1]."""
+    api._require_cuda(I, "I")
+    api._require_cuda(A, "A")
+    if A.dtype != torch.float64:
+        raise ValueError("A must be float64 (rti.design_matrix)")
+    _same_device(A=A, I=I)
+    _in_dtype(I)
+    I3 = I.contiguous() if I.dim() == 3 else I.contiguous().unsqueeze(0)
+    C, N, P = I3.shape
+    k = A.shape[1]
+    if A.shape[0] != N:
+        raise ValueError(f"A must be [{N}, k]; got {tuple(A.shape)}")
+    coef = torch.empty((C, k, P) if planar else (C, P, k), dtype=torch.float32, device=I.device)
+    res = torch.empty((C, P), dtype=torch.float32, device=I.device)
+    kept = torch.empty((C, P), dtype=torch.int32, device=I.device)
+    fallback = torch.zeros(1, dtype=torch.int32, device=I.device)
+    api.fit_robust_into(A.contiguous(), I3, coef, res, kept, fallback, k=k, lo=lo, hi=hi, min_lights=min_lights,
+                        iters=iters, delta=delta, layout="planar" if planar else "pixel", kernel=kernel)
+    if I.dim() == 2:
+        return coef[0], res[0], kept[0], fallback
+    return coef, res, kept, fallback
+
+
+@fit_robust.register_fake
+def _(A, I, lo, hi, min_lights, iters=0, delta=0.0, planar=False, kernel=0):
+    k = A.shape[1]
+    P = I.shape[-1]
+    lead = (I.shape[0],) if I.dim() == 3 else ()
+    return (I.new_empty(lead + ((k, P) if planar else (P, k)), dtype=torch.float32),
+            I.new_empty(lead + (P,), dtype=torch.float32),
+            I.new_empty(lead + (P,), dtype=torch.int32),
+            I.new_empty((1,), dtype=torch.int32))
 
 
 @torch.library.custom_op("rti::fit_residual", mutates_args=())
