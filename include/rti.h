@@ -299,6 +299,54 @@ int rti_fit_shared_robust(const double* A, int k, int N, const void* I, int in_d
                           float* res, int32_t* kept, int* fallback_px, int kernel, rti_stream_t stream);
 int rti_fit_shared_robust_plan(int k, int N, int in_dtype, int iters, int kernel);
 
+/* ---- device: the shared fit fed in chunks of light planes (rti_fit_accum.hip) -----------
+ * rti_fit_shared_residual's per-pixel sums kept in HBM between calls, for stacks that do not fit beside
+ * their outputs and for frames that arrive over time (analysis.py produces one intensity plane and one
+ * light direction per video frame).  Light n's contribution depends on light n alone, so planes can be
+ * fed any number at a time and a fit read out after any of them.
+ * state: device fp64, planar: element (c, j, p) at c*state_channel_stride + j*P + p
+ * (state_channel_stride 0 = (k+1)*P); planes j < k hold y_j = Σ_n R[n][j]·I[c][n][p], plane k holds
+ * q = Σ_n I[c][n][p]².  rti_fit_accum_state_doubles = C*(k+1)*P, the doubles a dense state holds, or -1
+ * for k outside {6, 9, 16}, P < 1 or C outside [1, 65535].
+ *
+ * rti_fit_accumulate adds one chunk of B >= 1 light planes (B = 1: a live frame).
+ *   R: device fp64 [B][k], the rows of THIS chunk's lights: rows of the design matrix A
+ *      (rti_design_matrix), or rows of U (rti_lsq_factors) when every direction is known in advance.
+ *   I: the chunk [C][B][P], light-major, F32 / U8 / I32; element (c, n, p) at
+ *      c*channel_stride + n*light_stride + p (light_stride 0 = P, channel_stride 0 = B*light_stride).
+ *   Per channel and pixel, for n = 0..B-1 in that order: x = (double)I[c][n][p],
+ *      y_j = fma(R[n][j], x, y_j) for each j, q = fma(x, x, q) -- one accumulator per (pixel, j), so the
+ *      state after N lights is bit-identical for every split of the N lights into chunks.
+ *   init != 0: the state is taken as zero and overwritten (it is not read; the caller need not zero it).
+ *   init == 0: the chunk is added to the state.
+ *   B*sizeof(element) + 8(k+1) (read; not with init) + 8(k+1) (write) bytes per pixel.
+ *
+ * rti_fit_accum_solve reads the state, leaves it unchanged (a preview after any chunk; accumulation can
+ * go on afterwards) and finishes the fit as rti_fit_shared_residual does:
+ *   M: device fp64 [k][k].  orth == 0: M = ginv (rti_gram_inverse) over ALL directions accumulated so
+ *      far, the state built from rows of A.  orth != 0: M = W (rti_lsq_factors), the state built from ALL
+ *      N rows of U (a prefix of U's rows is not an orthonormal basis: no preview in this form).
+ *   c_i = Σ_l M[i][l]·y_l (fma, l ascending from 0.0);  ss = q − Σ_i (orth ? y_i : c_i)·y_i;
+ *   ss < 0 -> 0, NaN passes;  res[c][p] = sqrt(ss / n_lights), fp32 [C][P], may be NULL;
+ *   coef: fp32, coef_layout / coef_channel_stride as rti_fit_shared.  n_lights: the lights accumulated.
+ *   8(k+1) bytes in and 4k + 4 out per pixel.
+ *
+ * Both: k ∈ {6, 9, 16} and F32 / U8 / I32 input, else RTI_ERR_UNSUPPORTED.  RTI_ERR_BAD_ARG: null
+ * R / I / state / M / coef; B, P, C or n_lights < 1; C > 65535; light_stride < P; with C > 1 a channel
+ * stride (input, state or coef) below its dense value; a bad coef_layout.  The vector path (16-byte
+ * loads) needs P and the strides multiples of 4 and 16-byte aligned bases; anything else runs one pixel
+ * per lane with the same arithmetic and bits. */
+int64_t rti_fit_accum_state_doubles(int k, int64_t P, int C);
+int rti_fit_accumulate(const double* R, int k, int B,
+                       const void* I, int in_dtype, int64_t P, int C,
+                       int64_t light_stride, int64_t channel_stride,
+                       double* state, int64_t state_channel_stride,
+                       int init, rti_stream_t stream);
+int rti_fit_accum_solve(const double* M, int k, int orth, int64_t n_lights,
+                        const double* state, int64_t P, int C, int64_t state_channel_stride,
+                        float* coef, int coef_layout, int64_t coef_channel_stride,
+                        float* res, rti_stream_t stream);
+
 /* ---- device: per-pixel PTM fit, light vectors generated in-kernel ------------------
  * Fuses compute_intensities' light vectors (analysis.py:221-231) into the
  * per-pixel PTM solve (analysis.py:280-298): for pixel (x, y) of an H×W stack

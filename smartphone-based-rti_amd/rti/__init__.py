@@ -6,18 +6,23 @@ bara96/Smartphone-based-RTI: analysis.py:196-411, interactive_relighting.py:11-3
     img = rti.relight(coef, 0.3, -0.2)               # [H, W]
     coef, res, kept = rti.fit_robust(I, lu, lv, lo=1, hi=254, iters=3, delta=5.0)  # clipped samples left out
 
+    acc = rti.FitAccumulator((H, W))                 # planes fed as they arrive, or a stack larger than HBM
+    for frame, u, v in frames: acc.add(frame, u, v)
+    coef, res = acc.solve()                          # any time: a preview, add() may go on
+
 Compute runs in HIP kernels of librti.so (include/rti.h); importing this
 package does not touch the GPU.
 """
 from . import _lib
 from ._lib import RTIError, RTILibraryMissing
-from .api import (BASES, apply_operator, basis_eval, basis_id, basis_operator, basis_terms, design_matrix, fit,
-                  fit_residual, fit_robust, fit_robust_into, fit_shared_into, fit_shared_residual_into, fit_with_residual,
+from .api import (BASES, FitAccumulator, apply_operator, basis_eval, basis_id, basis_operator, basis_terms,
+                  design_matrix, fit, fit_accum_solve_into, fit_accumulate_into, fit_chunked, fit_residual, fit_robust, fit_robust_into, fit_shared_into, fit_shared_residual_into, fit_with_residual,
                   gram_inverse,
                   interpolate_rbf, interpolate_rbf_perpixel, light_dirs, lsq_factors, pinv, q8_operator, h16_operator, rbf_operator,
                   relight, relight_frame)
 
-__all__ = ["BASES", "RTIError", "RTILibraryMissing", "apply_operator", "basis_eval", "basis_id", "basis_operator",
+__all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_into", "fit_chunked",
+           "RTIError", "RTILibraryMissing", "apply_operator", "basis_eval", "basis_id", "basis_operator",
            "basis_terms", "design_matrix", "fit", "fit_residual", "fit_robust", "fit_robust_into", "fit_shared_into",
            "fit_shared_residual_into",
            "fit_with_residual", "gram_inverse", "interpolate_rbf", "interpolate_rbf_perpixel", "light_dirs",

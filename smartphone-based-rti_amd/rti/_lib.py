@@ -116,6 +116,11 @@ SIGNATURES = {
                                        ctypes.c_float, ctypes.c_float, _c_int, _c_int, ctypes.c_float, _c_void_p,
                                        _c_int, _c_i64, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p]),
     "rti_fit_shared_robust_plan": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "rti_fit_accum_state_doubles": (_c_i64, [_c_int, _c_i64, _c_int]),
+    "rti_fit_accumulate": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_i64, _c_int, _c_i64, _c_i64,
+                                    _c_void_p, _c_i64, _c_int, _c_void_p]),
+    "rti_fit_accum_solve": (_c_int, [_c_void_p, _c_int, _c_int, _c_i64, _c_void_p, _c_i64, _c_int, _c_i64, _c_void_p,
+                                     _c_int, _c_i64, _c_void_p, _c_void_p]),
     "rti_fit_perpixel_cam": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_i64, _c_double,
                                       _c_double, _c_double, _c_void_p, _c_int, _c_int, _c_void_p]),
     "rti_fit_perpixel_dirs": (_c_int, [_c_void_p, _c_void_p, _c_void_p, _c_int, _c_int, _c_i64, _c_double,

@@ -628,6 +628,186 @@ def fit_robust(I, lu, lv, basis="ptm", *, lo=None, hi=None, min_lights=None, ite
     return (coef, res, kept) if I.dim() == 4 else (coef[0], res[0], kept[0])
 
 
+def fit_accumulate_into(R_dev, I3, state, *, k, init=False, light_stride=None):
+    """Launch ``rti_fit_accumulate`` on preallocated tensors (no allocation, graph-capturable): add the chunk's
+    B light planes to the fit state.
+
+    R_dev fp64 [B, k]: the chunk's rows of the design matrix (or of U from ``lsq_factors``).  I3 CUDA
+    [C, B, P] light-major (fp32/u8/int32); with ``light_stride`` > P it is a view of planes padded to that
+    many elements (channel stride B·light_stride).  state fp64 [C, k+1, P], contiguous.  ``init``: the
+    state is overwritten (never read), else added to."""
+    C, B, P = I3.shape
+    ls = P if light_stride is None else int(light_stride)
+    if state.dtype != torch.float64 or tuple(state.shape) != (C, k + 1, P) or not state.is_contiguous():
+        raise ValueError(f"state must be contiguous float64 [{C}, {k + 1}, {P}]; got {state.dtype} {tuple(state.shape)}")
+    if R_dev.dtype != torch.float64 or tuple(R_dev.shape) != (B, k) or not R_dev.is_contiguous():
+        raise ValueError(f"R must be contiguous float64 [{B}, {k}]; got {R_dev.dtype} {tuple(R_dev.shape)}")
+    want = (B * ls, ls, 1)
+    if ls < P or any(n > 1 and s != w for n, s, w in zip(I3.shape, I3.stride(), want)):
+        raise ValueError(f"I3 strides {tuple(I3.stride())} are not light-major planes of stride {ls}")
+    st = L.lib().rti_fit_accumulate(_vp(R_dev), k, B, _vp(I3), _IN_DTYPES[I3.dtype], P, C, ls, B * ls, _vp(state),
+                                    (k + 1) * P, 1 if init else 0, _stream_of(I3))
+    L.check(st, "rti_fit_accumulate")
+
+
+def fit_accum_solve_into(M_dev, state, coef, res, *, k, n_lights, orth=False, layout="pixel"):
+    """Launch ``rti_fit_accum_solve`` on preallocated tensors (no allocation, graph-capturable): coefficients
+    and residuals from a fit state, which stays as it is.
+
+    M_dev fp64 [k, k]: ``gram_inverse`` over every direction accumulated (state built from design rows), or
+    with ``orth`` W of ``lsq_factors`` (state built from all N rows of U).  state fp64 [C, k+1, P]; coef fp32
+    [C, P, k] / [C, k, P]; res fp32 [C, P] or None; n_lights: the lights accumulated."""
+    C, k1, P = state.shape
+    if state.dtype != torch.float64 or k1 != k + 1 or not state.is_contiguous():
+        raise ValueError(f"state must be contiguous float64 [C, {k + 1}, P]; got {state.dtype} {tuple(state.shape)}")
+    if M_dev.dtype != torch.float64 or tuple(M_dev.shape) != (k, k) or not M_dev.is_contiguous():
+        raise ValueError(f"M must be contiguous float64 [{k}, {k}]; got {M_dev.dtype} {tuple(M_dev.shape)}")
+    st = L.lib().rti_fit_accum_solve(_vp(M_dev), k, 1 if orth else 0, int(n_lights), _vp(state), P, C, (k + 1) * P,
+                                     _vp(coef), _layout_id(layout), P * k, None if res is None else _vp(res),
+                                     _stream_of(state))
+    L.check(st, "rti_fit_accum_solve")
+
+
+class FitAccumulator:
+    """The shared-direction fit fed in chunks of light planes (``rti_fit_accumulate`` /
+    ``rti_fit_accum_solve``): for stacks that do not fit in device memory and for frames that arrive over
+    time, as the reference's frame loop produces one intensity plane and one light direction per video frame.
+
+        acc = rti.FitAccumulator((H, W))
+        for frame, lu, lv in frames: acc.add(frame, lu, lv)      # CUDA [H, W] (or [B, H, W] with B directions)
+        coef, res = acc.solve()                                  # any time n_lights >= k; add() may go on
+
+    The device holds only ``state``: fp64 [C, k+1, P], per pixel y = Aᵀ I and ‖I‖² over the lights so far.
+    It does not depend on how the lights were split into chunks, to the bit.  ``solve`` is the Gram form,
+    coef = (AᵀA)⁺ y over every direction seen (cond(A)² in its rounding error).  With
+    ``directions=(lu_all, lv_all)`` given up front (the out-of-core case) the state is fed the rows of U of
+    the thin SVD instead and ``solve`` is the reference's SVD solve (cond(A), as ``fit_with_residual``);
+    ``add(frames)`` then takes the next rows in order, and ``solve`` needs all N planes.
+
+    shape: (H, W) or (P,).  channels=None: single-channel frames, outputs carry no leading C; channels=C:
+    frames are [C, B, H, W].  rcond: the SVD threshold of ``lsq_factors`` for ``directions`` (``solve`` takes
+    its own otherwise)."""
+
+    def __init__(self, shape, basis="ptm", *, channels=None, device="cuda", directions=None, rcond=None):
+        self.spatial = tuple(int(s) for s in shape)
+        if len(self.spatial) not in (1, 2) or min(self.spatial) < 1:
+            raise ValueError(f"shape must be (H, W) or (P,); got {shape!r}")
+        self.P = int(np.prod(self.spatial))
+        self.basis = basis_id(basis)
+        self.k = basis_terms(self.basis)
+        if channels is not None and int(channels) < 1:
+            raise ValueError(f"channels must be None or >= 1; got {channels!r}")
+        self.channels = None if channels is None else int(channels)
+        C = 1 if channels is None else self.channels
+        self.state = torch.empty((C, self.k + 1, self.P), dtype=torch.float64, device=device)  # the first add inits
+        _require_cuda(self.state, "device")
+        self._factors = None
+        if directions is not None:
+            lu, lv = directions
+            U, W = lsq_factors(lu, lv, self.basis, rcond)
+            if U.shape[0] < self.k:
+                raise ValueError(f"shapes not aligned: {U.shape[0]} lights < {self.k} basis terms (analysis.py:298)")
+            self._factors = (U, torch.as_tensor(W, device=self.state.device).contiguous())
+            self._dirs = (_f32_host(lu, "lu"), _f32_host(lv, "lv"))
+        self.reset()
+
+    def reset(self):
+        """Forget every light: the next ``add`` overwrites the state."""
+        self.n_lights = 0
+        self.lu, self.lv = [], []
+        return self
+
+    def _chunk(self, frames):
+        """frames -> [C, B, P] contiguous"""
+        _require_cuda(frames, "frames")
+        if frames.device != self.state.device:
+            raise ValueError(f"frames on {frames.device}, the accumulator on {self.state.device}")
+        if frames.dtype not in _IN_DTYPES:
+            raise ValueError(f"frames dtype {frames.dtype} unsupported (float32, uint8 or int32)")
+        sp, shp = self.spatial, tuple(frames.shape)
+        if self.channels is None:
+            if shp == sp:  # one frame
+                return frames.contiguous().reshape(1, 1, self.P)
+            if len(shp) >= 2 and (shp[1:] == sp or shp[1:] == (self.P,)):
+                return frames.contiguous().reshape(1, shp[0], self.P)
+            raise ValueError(f"frames {shp} are not {sp} planes ([H, W], [B, H, W] or [B, P])")
+        if len(shp) >= 3 and shp[0] == self.channels and (shp[2:] == sp or shp[2:] == (self.P,)):
+            return frames.contiguous().reshape(shp[0], shp[1], self.P)
+        raise ValueError(f"frames {shp} are not [C={self.channels}, B] + {sp} planes")
+
+    def add(self, frames, lu=None, lv=None):
+        """Add B light planes: CUDA [H, W] (one frame; lu, lv scalars), [B, H, W], [B, P] or, with channels,
+        [C, B, H, W]; float32 / uint8 / int32, and chunks of different dtypes may be mixed.  lu, lv: the B
+        directions (not with ``directions=``, where the planes take the next B rows in order)."""
+        I3 = self._chunk(frames)
+        B = I3.shape[1]
+        if self._factors is not None:
+            if lu is not None or lv is not None:
+                raise ValueError("this accumulator was given every direction up front: add(frames) takes no lu / lv")
+            U, (lu_all, lv_all) = self._factors[0], self._dirs
+            if self.n_lights + B > U.shape[0]:
+                raise ValueError(f"{self.n_lights + B} intensity planes for {U.shape[0]} light directions")
+            rows = U[self.n_lights:self.n_lights + B]
+            lu, lv = lu_all[self.n_lights:self.n_lights + B], lv_all[self.n_lights:self.n_lights + B]
+        else:
+            if lu is None or lv is None:
+                raise ValueError("add(frames, lu, lv): the planes' light directions are missing")
+            lu, lv = _f32_host(lu, "lu"), _f32_host(lv, "lv")
+            if lu.size != B or lv.size != B:
+                raise ValueError(f"{lu.size} / {lv.size} light directions for {B} intensity planes")
+            rows = design_matrix(lu, lv, self.basis)  # a row of A depends on its own light only
+        R_dev = torch.as_tensor(np.ascontiguousarray(rows), device=self.state.device)
+        fit_accumulate_into(R_dev, I3, self.state, k=self.k, init=self.n_lights == 0)
+        self.n_lights += B
+        self.lu.extend(float(x) for x in lu)
+        self.lv.extend(float(x) for x in lv)
+        return self
+
+    def solve(self, rcond=None, layout="pixel"):
+        """``(coef, res)`` of the lights added so far, shaped as ``fit_with_residual`` returns its first two
+        values; the state is left as it is (a preview: ``add`` may go on, ``solve`` may be repeated)."""
+        cl = _layout_id(layout)
+        k, P, N = self.k, self.P, self.n_lights
+        if N < k:
+            raise ValueError(f"shapes not aligned: {N} lights < {k} basis terms (analysis.py:298)")
+        dev = self.state.device
+        if self._factors is not None:
+            if rcond is not None:
+                raise ValueError("with directions= the SVD threshold is the constructor's rcond")
+            if N != self._factors[0].shape[0]:
+                raise ValueError(f"{N} of {self._factors[0].shape[0]} planes added: a prefix of U's rows is not an "
+                                 "orthonormal basis, so this form has no preview (omit directions= for one)")
+            M_dev, orth = self._factors[1], True
+        else:
+            ginv = gram_inverse(np.asarray(self.lu, np.float32), np.asarray(self.lv, np.float32), self.basis, rcond)
+            M_dev, orth = torch.as_tensor(ginv, device=dev).contiguous(), False
+        C = self.state.shape[0]
+        coef = torch.empty((C, P, k) if cl == L.RTI_COEF_PIXEL_MAJOR else (C, k, P), dtype=torch.float32, device=dev)
+        res = torch.empty((C, P), dtype=torch.float32, device=dev)
+        fit_accum_solve_into(M_dev, self.state, coef, res, k=k, n_lights=N, orth=orth, layout=cl)
+        sp = self.spatial
+        coef = coef.reshape((C,) + sp + (k,)) if cl == L.RTI_COEF_PIXEL_MAJOR else coef.reshape((C, k) + sp)
+        res = res.reshape((C,) + sp)
+        return (coef, res) if self.channels is not None else (coef[0], res[0])
+
+
+def fit_chunked(chunks, shape, basis="ptm", *, rcond=None, layout="pixel", **kw):
+    """The out-of-core shared fit: consume an iterable of ``(frames, lu, lv)`` chunks (with
+    ``directions=``: of ``frames``) through a ``FitAccumulator`` and return ``solve()``'s ``(coef, res)``.
+    The stack may live in host memory or on disk: CPU chunks are moved with
+    ``.to(device, non_blocking=True)`` (pinned chunks overlap the previous chunk's kernel; the producer
+    must not rewrite a pinned buffer before its copy has run).  kw: channels, device, directions."""
+    if kw.get("directions") is not None:
+        kw["rcond"] = rcond
+    acc = FitAccumulator(shape, basis, **kw)
+    for chunk in chunks:
+        frames, *d = chunk if isinstance(chunk, (tuple, list)) else (chunk,)
+        if torch.is_tensor(frames) and not frames.is_cuda:
+            frames = frames.to(acc.state.device, non_blocking=True)
+        acc.add(frames, *d)
+    return acc.solve(None if acc._factors is not None else rcond, layout)
+
+
 def light_dirs(cams, H, W, origin=(0.0, 0.0), device="cuda"):
     """compute_intensities' light vectors on the GPU: (lu, lv) fp32 [H, W, N]."""
     cams_d = torch.as_tensor(np.asarray(cams.detach().cpu() if torch.is_tensor(cams) else cams, np.float64),

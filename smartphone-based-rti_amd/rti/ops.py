@@ -1,5 +1,5 @@
 """PyTorch custom ops over the C ABI: ``torch.ops.rti.fit_shared`` / ``fit_shared_residual`` /
-``fit_robust`` / ``fit_residual`` / ``relight``.
+``fit_robust`` / ``fit_accumulate`` / ``fit_accum_solve`` / ``fit_residual`` / ``relight``.
 
 They let the fit and relight kernels sit inside torch programs (and
 ``torch.library`` fake-tensor tracing) while the compute stays in librti's
@@ -141,6 +141,67 @@ def _(A, I, lo, hi, min_lights, iters=0, delta=0.0, planar=False, kernel=0):
             I.new_empty(lead + (P,), dtype=torch.float32),
             I.new_empty(lead + (P,), dtype=torch.int32),
             I.new_empty((1,), dtype=torch.int32))
+
+
+def _accum_state(state, k):
+    if state.dtype != torch.float64 or state.dim() not in (2, 3) or state.shape[-2] != k + 1:
+        raise ValueError(f"state must be float64 [{k + 1}, P] or [C, {k + 1}, P]; got {state.dtype} {tuple(state.shape)}")
+    if not state.is_contiguous():
+        raise ValueError("state must be contiguous")
+    return state if state.dim() == 3 else state.unsqueeze(0)
+
+
+@torch.library.custom_op("rti::fit_accumulate", mutates_args=("state",))
+def fit_accumulate(R: torch.Tensor, I: torch.Tensor, state: torch.Tensor, init: bool) -> None:
+    """Add a chunk of light planes to a fit state in place (``rti_fit_accumulate``).  R fp64 CUDA [B, k]: the
+    chunk's rows of the design matrix (or of U); I CUDA [B, P] or [C, B, P] (fp32/u8/int32); state fp64
+    [k+1, P] or [C, k+1, P]; init: overwrite the state instead of adding to it."""
+    api._require_cuda(I, "I")
+    api._require_cuda(R, "R")
+    api._require_cuda(state, "state")
+    _same_device(R=R, I=I, state=state)
+    _in_dtype(I)
+    if I.dim() != state.dim() or I.dim() not in (2, 3):
+        raise ValueError(f"I {tuple(I.shape)} and state {tuple(state.shape)} must both be 2-D or both 3-D")
+    k = R.shape[1]
+    s3 = _accum_state(state, k)
+    I3 = I.contiguous() if I.dim() == 3 else I.contiguous().unsqueeze(0)
+    if I3.shape[0] != s3.shape[0] or I3.shape[2] != s3.shape[2]:
+        raise ValueError(f"I {tuple(I.shape)} does not match state {tuple(state.shape)}")
+    api.fit_accumulate_into(R.contiguous(), I3, s3, k=k, init=init)
+
+
+@fit_accumulate.register_fake
+def _(R, I, state, init):
+    return None
+
+
+@torch.library.custom_op("rti::fit_accum_solve", mutates_args=())
+def fit_accum_solve(M: torch.Tensor, state: torch.Tensor, n_lights: int, orth: bool = False,
+                    planar: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+    """Coefficients and residuals from a fit state (``rti_fit_accum_solve``).  M fp64 CUDA [k, k]
+    (``rti.gram_inverse`` over every direction accumulated, or W of ``rti.lsq_factors`` with orth); state fp64
+    [k+1, P] or [C, k+1, P] -> ``(coef, res)``: coef fp32 [C?, P, k] (or [C?, k, P] if planar), res fp32 [C?, P]."""
+    api._require_cuda(M, "M")
+    api._require_cuda(state, "state")
+    _same_device(M=M, state=state)
+    k = M.shape[0]
+    s3 = _accum_state(state, k)
+    C, _, P = s3.shape
+    coef = torch.empty((C, k, P) if planar else (C, P, k), dtype=torch.float32, device=state.device)
+    res = torch.empty((C, P), dtype=torch.float32, device=state.device)
+    api.fit_accum_solve_into(M.contiguous(), s3, coef, res, k=k, n_lights=n_lights, orth=orth,
+                             layout="planar" if planar else "pixel")
+    return (coef, res) if state.dim() == 3 else (coef[0], res[0])
+
+
+@fit_accum_solve.register_fake
+def _(M, state, n_lights, orth=False, planar=False):
+    k = M.shape[0]
+    P = state.shape[-1]
+    lead = (state.shape[0],) if state.dim() == 3 else ()
+    return (state.new_empty(lead + ((k, P) if planar else (P, k)), dtype=torch.float32),
+            state.new_empty(lead + (P,), dtype=torch.float32))
 
 
 @torch.library.custom_op("rti::fit_residual", mutates_args=())
