@@ -32,6 +32,7 @@
 
 #include "rti_basis.h"
 #include "rti_internal.h"
+#include "rti_stack.h"
 
 namespace rti {
 
@@ -71,8 +72,6 @@ hipError_t reserve_lds(const void* kern, size_t bytes) {
 }
 
 namespace {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 // ---- VEC adjacent pixels of one light plane -> fp32 registers ------------------------
 template <typename T, int VEC, bool NT>
@@ -1267,16 +1266,6 @@ int launch_tile(const FitArgs& a, int rc, int sp, int depth, int waves) {
   return RTI_OK;
 }
 
-size_t dtype_size(int dt) {
-  switch (dt) {
-    case RTI_F32: return 4;
-    case RTI_I32: return 4;
-    case RTI_U8: return 1;
-    case RTI_F64: return 8;
-    default: return 0;
-  }
-}
-
 // ---- launch generations (r02) ---------------------------------------------------------------
 // The stack streams fastest when every wave on the chip sweeps the light planes in step with the
 // others, so that at any moment they all read one contiguous slab of the same plane.  The waves of
@@ -1384,43 +1373,29 @@ extern "C" int rti_fit_shared(const float* pinv, int k, int N, const void* I, in
                         RTI_FIELD_TILE_PLANES | RTI_FIELD_TILE_DEPTH | RTI_FIELD_TILE_WAVES;
   if (!kernel_bits_ok(kernel, RTI_KERNEL_TILE, flags))
     return fail(RTI_ERR_BAD_ARG, "rti_fit_shared: unknown kernel bits 0x%x", kernel);
-  if (!pinv || !I || !coef) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared: null pointer");
-  if (N <= 0 || P <= 0 || C <= 0 || C > 65535) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared: bad N/P/C");
-  if (k < 1 || k > 16) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared: k=%d outside 1..16", k);
-  if (N < k) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared: N=%d < k=%d", N, k);
-  if (in_dtype != RTI_F32 && in_dtype != RTI_U8 && in_dtype != RTI_I32)
-    return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared: input dtype %d", in_dtype);
-  if (coef_layout != RTI_COEF_PIXEL_MAJOR && coef_layout != RTI_COEF_PLANAR)
-    return fail(RTI_ERR_BAD_ARG, "rti_fit_shared: coef layout %d", coef_layout);
+  const char* const E = "rti_fit_shared";
+  if (int st = check_pointers(E, {pinv, I, coef})) return st;
+  if (int st = check_extents(E, "N/P/C", N, P, C)) return st;
+  if (k < 1 || k > 16) return fail(RTI_ERR_BAD_ARG, "%s: k=%d outside 1..16", E, k);
+  if (int st = check_lights(E, N, k)) return st;
+  if (int st = check_in_dtype(E, in_dtype)) return st;
+  if (int st = check_coef_layout(E, coef_layout)) return st;
   note_launches(1);
-  FitArgs a;
-  a.pinv = pinv;
-  a.k = k;
-  a.N = N;
-  a.I = I;
-  a.P = P;
-  a.C = C;
-  a.lstride = light_stride ? light_stride : P;
-  a.cstride = channel_stride ? channel_stride : (int64_t)N * a.lstride;
-  a.coef = coef;
-  a.layout = coef_layout;
-  a.ocstride = coef_channel_stride ? coef_channel_stride : P * k;
-  a.nt = (kernel & RTI_KERNEL_NONTEMPORAL) != 0;
-  a.mode = (a.nt ? VM_NT : 0) | ((kernel & RTI_KERNEL_PINV_LDS) ? VM_LDS : 0) |
-           ((kernel & RTI_KERNEL_NT_STORE) ? VM_NTS : 0) | ((kernel & RTI_KERNEL_STAGE) ? VM_STAGE : 0);
-  if ((a.mode & VM_LDS) && (size_t)N * 16 * sizeof(float) > 24576) a.mode &= ~VM_LDS;  // keep LDS <= 64 KiB
-  a.nc = (kernel >> RTI_KERNEL_CHUNKS_SHIFT) & 0xF;  // 0 = AUTO below
-  a.stream = (hipStream_t)stream;
-  if (a.lstride < P) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared: light_stride < P");
-  if (C > 1 && a.cstride < (int64_t)N * a.lstride) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared: channel_stride");
-  if (C > 1 && a.ocstride < P * k) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared: coef_channel_stride");
+  const StackView in = stack_view(I, in_dtype, N, P, C, light_stride, channel_stride);
+  const CoefView out = coef_view(coef, coef_layout, k, P, coef_channel_stride);
+  const bool nt = (kernel & RTI_KERNEL_NONTEMPORAL) != 0;
+  int mode = (nt ? VM_NT : 0) | ((kernel & RTI_KERNEL_PINV_LDS) ? VM_LDS : 0) |
+             ((kernel & RTI_KERNEL_NT_STORE) ? VM_NTS : 0) | ((kernel & RTI_KERNEL_STAGE) ? VM_STAGE : 0);
+  if ((mode & VM_LDS) && (size_t)N * 16 * sizeof(float) > 24576) mode &= ~VM_LDS;  // keep LDS <= 64 KiB
+  FitArgs a{pinv, k, N, I, P, C, in.lstride, in.cstride, coef, coef_layout, out.ocstride, nt, mode,
+            (kernel >> RTI_KERNEL_CHUNKS_SHIFT) & 0xF /* nc: 0 = AUTO below */, (hipStream_t)stream};
+  if (int st = check_stack_strides(E, in)) return st;
+  if (int st = check_coef_stride(E, out, P, C)) return st;
 
-  const size_t es = dtype_size(in_dtype);
+  const size_t es = in.es;
   auto vec_ok_for = [&](int vec) {
-    const bool in_ok = P % vec == 0 && a.lstride % vec == 0 && a.cstride % vec == 0 && aligned_to(I, vec * es);
-    const bool out_ok = aligned_to(coef, 16) && (a.ocstride % 4 == 0) &&
-                        (coef_layout == RTI_COEF_PLANAR ? P % 4 == 0 : (vec * k) % 4 == 0);
-    return in_ok && out_ok;
+    return stack_vec_ok_any_c(in, vec) && coef_vec_ok_any_c(out) &&
+           (coef_layout == RTI_COEF_PLANAR ? P % 4 == 0 : (vec * k) % 4 == 0);
   };
   const int sel = kernel & 0xff;
   const bool valu_k = (k == 6 || k == 9 || k == 16);
@@ -1478,8 +1453,7 @@ extern "C" int rti_fit_shared(const float* pinv, int k, int N, const void* I, in
         }
     }
   }
-  const bool mfma_ok = N <= 1024 && P % 4 == 0 && a.lstride % 4 == 0 && a.cstride % 4 == 0 &&
-                       aligned_to(I, 4 * es) && aligned_to(coef, 16) && a.ocstride % 4 == 0;
+  const bool mfma_ok = N <= 1024 && stack_vec_ok_any_c(in, 4) && coef_vec_ok_any_c(out);
   // AUTO for HSH-16 on fp32 stacks: the LDS-tiled MFMA kernel (c4 4K RGB x 200: 3.54 vs 3.73 ms
   // and 3.94 vs 4.20 ms on two boxes, profiles/r01_c4_tile_sweep.log), when the image gives at
   // least 1024 tiles of 2048 pixels; PTM-6 stays on the VALU stream (c3: 0.54 vs 0.62 ms).
@@ -1532,11 +1506,7 @@ extern "C" int rti_fit_shared(const float* pinv, int k, int N, const void* I, in
   if (!use_mfma && !valu_k) return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared: VALU path supports k in {6,9,16}");
 
   if (use_mfma) {
-    switch (in_dtype) {
-      case RTI_F32: launch_mfma<float>(a); break;
-      case RTI_I32: launch_mfma<int32_t>(a); break;
-      default: launch_mfma<uint8_t>(a); break;
-    }
+    with_in_dtype(in_dtype, [&](auto t) { launch_mfma<decltype(t)>(a); });
   } else {
     const int vec = in_dtype == RTI_U8 ? (k <= 6 ? 16 : 4) : 4;
     const bool vok = vec_ok_for(vec);

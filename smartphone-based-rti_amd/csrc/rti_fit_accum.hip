@@ -26,27 +26,14 @@
 #include <cmath>
 #include <cstdint>
 
-#include "rti_internal.h"
+#include "rti_lsq.h"
+#include "rti_stack.h"
 
 namespace rti {
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
 typedef double doublex2 __attribute__((ext_vector_type(2)));
 constexpr int FA_THREADS = 256;
-
-template <typename T, int VEC>
-__device__ __forceinline__ void load_nt(const T* __restrict__ p, T (&x)[VEC]) {
-  if constexpr (VEC == 1) {
-    x[0] = __builtin_nontemporal_load(p);
-  } else {
-    typedef T vec_t __attribute__((ext_vector_type(VEC)));
-    const vec_t v = __builtin_nontemporal_load(reinterpret_cast<const vec_t*>(p));
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) x[i] = v[i];
-  }
-}
 
 // VEC consecutive doubles of a state plane (VEC even: 16-byte loads / stores)
 template <int VEC>
@@ -107,13 +94,13 @@ fit_accumulate_k(const double* __restrict__ R, int B, const T* __restrict__ I, i
   for (; n + U <= B; n += U) {  // U plane loads in flight per lane
     T x[U][VEC];
 #pragma unroll
-    for (int u = 0; u < U; ++u) load_nt<T, VEC>(src + (int64_t)(n + u) * lstride, x[u]);
+    for (int u = 0; u < U; ++u) load_nt<T>(src + (int64_t)(n + u) * lstride, x[u]);
 #pragma unroll
     for (int u = 0; u < U; ++u) add_plane<K, VEC, T>(R + (int64_t)(n + u) * K, x[u], y);  // wave-uniform row -> SGPRs
   }
   for (; n < B; ++n) {  // the last B % U planes; the whole chunk for a live frame (B = 1)
     T x[VEC];
-    load_nt<T, VEC>(src + (int64_t)n * lstride, x);
+    load_nt<T>(src + (int64_t)n * lstride, x);
     add_plane<K, VEC, T>(R + (int64_t)n * K, x, y);
   }
 #pragma unroll
@@ -141,7 +128,8 @@ fit_accum_solve_k(const double* __restrict__ M, int orth, int64_t n_lights, cons
 #pragma unroll
   for (int j = 0; j <= K; ++j) load_state<VEC>(st + (int64_t)j * P, y[j]);
 
-  // the tail of fitres_body (rti_fitres.hip), restated: c_i = Σ_l M[i][l]·y_l, ss = q − Σ_i (orth ? y_i : c_i)·y_i
+  // the tail of fitres_body (rti_fitres.hip), restated: c_i = Σ_l M[i][l]·y_l, ss = q − Σ_i (orth ? y_i : c_i)·y_i;
+  // tests/test_gpu_accum.py::test_same_bits_as_one_pass_fit holds the two copies to the same bits
   const double invN = 1.0 / (double)n_lights;
   float o[F], r[VEC];
 #pragma unroll
@@ -209,10 +197,7 @@ fit_accum_solve_k(const double* __restrict__ M, int orth, int64_t n_lights, cons
 
 struct AccArgs {
   const double* R;
-  int B;
-  const void* I;
-  int64_t P, lstride, cstride;
-  int C;
+  StackView in;  // the chunk: N = its B planes
   double* state;
   int64_t scstride;
   bool init;
@@ -221,13 +206,14 @@ struct AccArgs {
 
 template <int K, int VEC, int U, typename T>
 int launch_acc_t(const AccArgs& a) {
-  const dim3 grid(grid_1d(a.P, FA_THREADS * VEC), a.C);
+  const StackView& in = a.in;
+  const dim3 grid(grid_1d(in.P, FA_THREADS * VEC), in.C);
   if (a.init)
-    hipLaunchKernelGGL((fit_accumulate_k<K, VEC, U, T, true>), grid, dim3(FA_THREADS), 0, a.s, a.R, a.B,
-                       static_cast<const T*>(a.I), a.P, a.lstride, a.cstride, a.state, a.scstride);
+    hipLaunchKernelGGL((fit_accumulate_k<K, VEC, U, T, true>), grid, dim3(FA_THREADS), 0, a.s, a.R, in.N,
+                       static_cast<const T*>(in.I), in.P, in.lstride, in.cstride, a.state, a.scstride);
   else
-    hipLaunchKernelGGL((fit_accumulate_k<K, VEC, U, T, false>), grid, dim3(FA_THREADS), 0, a.s, a.R, a.B,
-                       static_cast<const T*>(a.I), a.P, a.lstride, a.cstride, a.state, a.scstride);
+    hipLaunchKernelGGL((fit_accumulate_k<K, VEC, U, T, false>), grid, dim3(FA_THREADS), 0, a.s, a.R, in.N,
+                       static_cast<const T*>(in.I), in.P, in.lstride, in.cstride, a.state, a.scstride);
   return check_launch("rti_fit_accumulate");
 }
 
@@ -254,8 +240,7 @@ struct SolveArgs {
   const double* state;
   int64_t P, scstride;
   int C;
-  float* coef;
-  int64_t ocstride;
+  CoefView out;
   float* res;
   hipStream_t s;
 };
@@ -264,7 +249,7 @@ template <int K, int VEC, int LAYOUT>
 int launch_solve_t(const SolveArgs& a) {
   const dim3 grid(grid_1d(a.P, FA_THREADS * VEC), a.C);
   hipLaunchKernelGGL((fit_accum_solve_k<K, VEC, LAYOUT>), grid, dim3(FA_THREADS), 0, a.s, a.M, a.orth, a.n_lights, a.state,
-                     a.P, a.scstride, a.coef, a.ocstride, a.res);
+                     a.P, a.scstride, a.out.coef, a.out.ocstride, a.res);
   return check_launch("rti_fit_accum_solve");
 }
 
@@ -299,62 +284,35 @@ extern "C" int64_t rti_fit_accum_state_doubles(int k, int64_t P, int C) {
 extern "C" int rti_fit_accumulate(const double* R, int k, int B, const void* I, int in_dtype, int64_t P, int C,
                                   int64_t light_stride, int64_t channel_stride, double* state,
                                   int64_t state_channel_stride, int init, rti_stream_t stream) {
-  if (!R || !I || !state) return fail(RTI_ERR_BAD_ARG, "rti_fit_accumulate: null pointer");
-  if (B < 1 || P < 1 || C < 1 || C > 65535) return fail(RTI_ERR_BAD_ARG, "rti_fit_accumulate: bad B/P/C");
-  if (!accum_k_ok(k)) return fail(RTI_ERR_UNSUPPORTED, "rti_fit_accumulate: k=%d (supported: 6, 9, 16)", k);
-  if (in_dtype != RTI_F32 && in_dtype != RTI_U8 && in_dtype != RTI_I32)
-    return fail(RTI_ERR_UNSUPPORTED, "rti_fit_accumulate: input dtype %d", in_dtype);
-  AccArgs a;
-  a.R = R;
-  a.B = B;
-  a.I = I;
-  a.P = P;
-  a.C = C;
-  a.lstride = light_stride ? light_stride : P;
-  a.cstride = channel_stride ? channel_stride : (int64_t)B * a.lstride;
-  a.state = state;
-  a.scstride = state_channel_stride ? state_channel_stride : (int64_t)(k + 1) * P;
-  a.init = init != 0;
-  a.s = (hipStream_t)stream;
-  if (a.lstride < P) return fail(RTI_ERR_BAD_ARG, "rti_fit_accumulate: light_stride < P");
-  if (C > 1 && a.cstride < (int64_t)B * a.lstride) return fail(RTI_ERR_BAD_ARG, "rti_fit_accumulate: channel_stride");
-  if (C > 1 && a.scstride < (int64_t)(k + 1) * P)
-    return fail(RTI_ERR_BAD_ARG, "rti_fit_accumulate: state_channel_stride");
-  const size_t es = in_dtype == RTI_U8 ? 1 : 4;
-  const bool vec4 = P % 4 == 0 && a.lstride % 4 == 0 && (C == 1 || a.cstride % 4 == 0) && aligned_to(I, 4 * es) &&
-                    aligned_to(state, 16) && (C == 1 || a.scstride % 2 == 0);
-  switch (in_dtype) {
-    case RTI_F32: return launch_acc_k<float>(k, a, vec4);
-    case RTI_U8: return launch_acc_k<uint8_t>(k, a, vec4);
-    default: return launch_acc_k<int32_t>(k, a, vec4);
-  }
+  const char* const E = "rti_fit_accumulate";
+  if (int st = check_pointers(E, {R, I, state})) return st;
+  if (int st = check_extents(E, "B/P/C", B, P, C)) return st;
+  if (!accum_k_ok(k)) return fail(RTI_ERR_UNSUPPORTED, "%s: k=%d (supported: 6, 9, 16)", E, k);
+  if (int st = check_in_dtype(E, in_dtype)) return st;
+  const int64_t scstride = state_channel_stride ? state_channel_stride : (int64_t)(k + 1) * P;
+  const AccArgs a{R, stack_view(I, in_dtype, B, P, C, light_stride, channel_stride), state, scstride, init != 0,
+                  (hipStream_t)stream};
+  if (int st = check_stack_strides(E, a.in)) return st;
+  if (C > 1 && scstride < (int64_t)(k + 1) * P) return fail(RTI_ERR_BAD_ARG, "%s: state_channel_stride", E);
+  const bool vec4 = stack_vec_ok_used(a.in, 4) && aligned_to(state, 16) && (C == 1 || scstride % 2 == 0);
+  return with_in_dtype(in_dtype, [&](auto t) { return launch_acc_k<decltype(t)>(k, a, vec4); });
 }
 
 extern "C" int rti_fit_accum_solve(const double* M, int k, int orth, int64_t n_lights, const double* state, int64_t P,
                                    int C, int64_t state_channel_stride, float* coef, int coef_layout,
                                    int64_t coef_channel_stride, float* res, rti_stream_t stream) {
-  if (!M || !state || !coef) return fail(RTI_ERR_BAD_ARG, "rti_fit_accum_solve: null pointer");
-  if (n_lights < 1 || P < 1 || C < 1 || C > 65535) return fail(RTI_ERR_BAD_ARG, "rti_fit_accum_solve: bad n_lights/P/C");
-  if (!accum_k_ok(k)) return fail(RTI_ERR_UNSUPPORTED, "rti_fit_accum_solve: k=%d (supported: 6, 9, 16)", k);
-  if (coef_layout != RTI_COEF_PIXEL_MAJOR && coef_layout != RTI_COEF_PLANAR)
-    return fail(RTI_ERR_BAD_ARG, "rti_fit_accum_solve: coef layout %d", coef_layout);
-  SolveArgs a;
-  a.M = M;
-  a.orth = orth ? 1 : 0;
-  a.n_lights = n_lights;
-  a.state = state;
-  a.P = P;
-  a.C = C;
-  a.scstride = state_channel_stride ? state_channel_stride : (int64_t)(k + 1) * P;
-  a.coef = coef;
-  a.ocstride = coef_channel_stride ? coef_channel_stride : P * k;
-  a.res = res;
-  a.s = (hipStream_t)stream;
-  if (C > 1 && a.scstride < (int64_t)(k + 1) * P)
-    return fail(RTI_ERR_BAD_ARG, "rti_fit_accum_solve: state_channel_stride");
-  if (C > 1 && a.ocstride < P * k) return fail(RTI_ERR_BAD_ARG, "rti_fit_accum_solve: coef_channel_stride");
-  const bool vec = P % 4 == 0 && aligned_to(state, 16) && (C == 1 || a.scstride % 2 == 0) && aligned_to(coef, 16) &&
-                   (C == 1 || a.ocstride % 4 == 0) && (!res || aligned_to(res, 16));
+  const char* const E = "rti_fit_accum_solve";
+  if (int st = check_pointers(E, {M, state, coef})) return st;
+  if (int st = check_extents(E, "n_lights/P/C", n_lights, P, C)) return st;
+  if (!accum_k_ok(k)) return fail(RTI_ERR_UNSUPPORTED, "%s: k=%d (supported: 6, 9, 16)", E, k);
+  if (int st = check_coef_layout(E, coef_layout)) return st;
+  const int64_t scstride = state_channel_stride ? state_channel_stride : (int64_t)(k + 1) * P;
+  const SolveArgs a{M, orth ? 1 : 0, n_lights, state, P, scstride, C, coef_view(coef, coef_layout, k, P, coef_channel_stride),
+                    res, (hipStream_t)stream};
+  if (C > 1 && scstride < (int64_t)(k + 1) * P) return fail(RTI_ERR_BAD_ARG, "%s: state_channel_stride", E);
+  if (int st = check_coef_stride(E, a.out, P, C)) return st;
+  const bool vec = P % 4 == 0 && aligned_to(state, 16) && (C == 1 || scstride % 2 == 0) && coef_vec_ok_used(a.out, C) &&
+                   (!res || aligned_to(res, 16));
   return coef_layout == RTI_COEF_PLANAR ? launch_solve_k<RTI_COEF_PLANAR>(k, a, vec ? 4 : 1)
                                         : launch_solve_k<RTI_COEF_PIXEL_MAJOR>(k, a, vec ? 4 : 1);
 }

@@ -23,13 +23,12 @@
 #include <cstdint>
 
 #include "rti_internal.h"
+#include "rti_stack.h"
 
 namespace rti {
 namespace {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v2i __attribute__((ext_vector_type(2)));
 
@@ -335,13 +334,8 @@ int launch_h16_t(const unsigned char* op, int N, const unsigned char* I, int64_t
 
 struct H16Args {
   const unsigned char* op;
-  int N;
-  const unsigned char* I;
-  int64_t P;
-  int C;
-  int64_t ls, cs;
-  float* coef;
-  int64_t ocs;
+  StackView in;  // u8
+  CoefView out;
   int want;  // RTI_KERNEL_CHUNKS: tiles per workgroup (0 = AUTO)
   int cb;    // RTI_KERNEL_TILE_DEPTH: batched groups (measurement)
   hipStream_t s;
@@ -351,10 +345,12 @@ struct H16Args {
 template <int K, int LAYOUT, int R, int STEP, int W = H16_W>
 int launch_h16_g(const H16Args& a) {
   // one workgroup per CU over all channels, each streaming tpw interleaved tiles
-  const int64_t tpc = (a.P + R - 1) / R, cus = device_cus();
-  const int64_t wpc = (cus >= a.C ? cus / a.C : 1) * (2048 / R);  // workgroups per channel: 2048/R per CU
+  const StackView& in = a.in;
+  const int64_t tpc = (in.P + R - 1) / R, cus = device_cus();
+  const int64_t wpc = (cus >= in.C ? cus / in.C : 1) * (2048 / R);  // workgroups per channel: 2048/R per CU
   const int tpw = a.want ? a.want : (int)((tpc + wpc - 1) / wpc);
-  return launch_h16_t<K, LAYOUT, R, STEP, W>(a.op, a.N, a.I, a.P, a.C, a.ls, a.cs, a.coef, a.ocs, tpw, a.cb, a.s);
+  return launch_h16_t<K, LAYOUT, R, STEP, W>(a.op, in.N, static_cast<const unsigned char*>(in.I), in.P, in.C, in.lstride,
+                                             in.cstride, a.out.coef, a.out.ocstride, tpw, a.cb, a.s);
 }
 
 // AUTO geometry: 1024-pixel tiles (1-KiB runs per wave and plane, two workgroups per CU) for k <= 9 where two
@@ -367,13 +363,14 @@ bool h16_half_tiles(int k, int N, int geom) {
 }
 
 template <int K>
-int launch_h16_l(int layout, const H16Args& a) {
+int launch_h16_l(const H16Args& a) {
+  const int layout = a.out.layout;
   // the 2048-pixel tile on 16 waves (2-KiB runs per plane and wave; AUTO where the 1024-pixel tile is not):
   // c4 u8 1.282 vs 1.308 ms on 8 waves, c3 u8 0.1866 vs 0.1866 on 1024-pixel tiles (profiles/r05w_h16_geometry_*)
-  if (a.geom == 3 || (a.geom == 0 && !h16_half_tiles(K, a.N, 0)))
+  if (a.geom == 3 || (a.geom == 0 && !h16_half_tiles(K, a.in.N, 0)))
     return layout == RTI_COEF_PLANAR ? launch_h16_g<K, RTI_COEF_PLANAR, 2048, 32, 16>(a)
                                      : launch_h16_g<K, RTI_COEF_PIXEL_MAJOR, 2048, 32, 16>(a);
-  if (h16_half_tiles(K, a.N, a.geom))
+  if (h16_half_tiles(K, a.in.N, a.geom))
     return layout == RTI_COEF_PLANAR ? launch_h16_g<K, RTI_COEF_PLANAR, 1024, 32>(a)
                                      : launch_h16_g<K, RTI_COEF_PIXEL_MAJOR, 1024, 32>(a);
   return layout == RTI_COEF_PLANAR ? launch_h16_g<K, RTI_COEF_PLANAR, 2048, 32>(a)
@@ -434,33 +431,30 @@ extern "C" int rti_fit_shared_h16(const void* op, int k, int N, const uint8_t* I
                                   int64_t coef_channel_stride, int kernel, rti_stream_t stream) {
   if (!kernel_bits_ok(kernel, RTI_KERNEL_AUTO, RTI_FIELD_CHUNKS | RTI_FIELD_TILE_DEPTH | RTI_FIELD_TILE_WAVES))
     return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_h16: unknown kernel bits 0x%x", kernel);
-  if (!op || !I || !coef) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_h16: null pointer");
-  if (N <= 0 || P <= 0 || C <= 0 || C > 65535) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_h16: bad N/P/C");
-  if (N < k) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_h16: N=%d < k=%d", N, k);
-  if (coef_layout != RTI_COEF_PIXEL_MAJOR && coef_layout != RTI_COEF_PLANAR)
-    return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_h16: coef layout %d", coef_layout);
+  const char* const E = "rti_fit_shared_h16";
+  if (int st = check_pointers(E, {op, I, coef})) return st;
+  if (int st = check_extents(E, "N/P/C", N, P, C)) return st;
+  if (int st = check_lights(E, N, k)) return st;
+  if (int st = check_coef_layout(E, coef_layout)) return st;
   if (N > rti_fit_shared_h16_max_lights())
-    return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_h16: N=%d > %d (LDS)", N, rti_fit_shared_h16_max_lights());
-  const int64_t ls = light_stride ? light_stride : P;
-  const int64_t cs = channel_stride ? channel_stride : (int64_t)N * ls;
-  const int64_t ocs = coef_channel_stride ? coef_channel_stride : P * k;
-  if (ls < P) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_h16: light_stride < P");
-  if (C > 1 && cs < (int64_t)N * ls) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_h16: channel_stride");
-  if (C > 1 && ocs < P * k) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_h16: coef_channel_stride");
-  if (P > 0x7fffff00)  // plane offsets are 32-bit buffer offsets
-    return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_h16: P=%lld pixels per plane", (long long)P);
-  if (P % 16 || ls % 16 || cs % 16 || !aligned_to(I, 16) || !aligned_to(op, 16) || !aligned_to(coef, 16) || ocs % 4)
-    return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_h16: needs P, strides and pointers 16-byte aligned");
-  note_launches(1);
+    return fail(RTI_ERR_UNSUPPORTED, "%s: N=%d > %d (LDS)", E, N, rti_fit_shared_h16_max_lights());
   // RTI_KERNEL_CHUNKS(n): tiles per workgroup = n; RTI_KERNEL_TILE_DEPTH(1|4|8): groups batched per round;
   // RTI_KERNEL_TILE_WAVES(1|2|3): the 2048- or 1024-pixel tile, or 2048 pixels on 16 waves (measurement)
-  const H16Args a{static_cast<const unsigned char*>(op), N, I, P, C, ls, cs, coef, ocs,
-                  (kernel >> RTI_KERNEL_CHUNKS_SHIFT) & 0xF, (kernel >> RTI_KERNEL_TILE_DEPTH_SHIFT) & 0xF,
-                  (hipStream_t)stream, (kernel >> RTI_KERNEL_TILE_WAVES_SHIFT) & 0xF};
+  const H16Args a{static_cast<const unsigned char*>(op), stack_view(I, RTI_U8, N, P, C, light_stride, channel_stride),
+                  coef_view(coef, coef_layout, k, P, coef_channel_stride), (kernel >> RTI_KERNEL_CHUNKS_SHIFT) & 0xF,
+                  (kernel >> RTI_KERNEL_TILE_DEPTH_SHIFT) & 0xF, (hipStream_t)stream,
+                  (kernel >> RTI_KERNEL_TILE_WAVES_SHIFT) & 0xF};
+  if (int st = check_stack_strides(E, a.in)) return st;
+  if (int st = check_coef_stride(E, a.out, P, C)) return st;
+  if (P > 0x7fffff00)  // plane offsets are 32-bit buffer offsets
+    return fail(RTI_ERR_UNSUPPORTED, "%s: P=%lld pixels per plane", E, (long long)P);
+  if (!stack_vec_ok_any_c(a.in, 16) || !aligned_to(op, 16) || !coef_vec_ok_any_c(a.out))
+    return fail(RTI_ERR_UNSUPPORTED, "%s: needs P, strides and pointers 16-byte aligned", E);
+  note_launches(1);
   switch (k) {
-    case 6: return launch_h16_l<6>(coef_layout, a);
-    case 9: return launch_h16_l<9>(coef_layout, a);
-    case 16: return launch_h16_l<16>(coef_layout, a);
-    default: return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_h16: k=%d (supported: 6, 9, 16)", k);
+    case 6: return launch_h16_l<6>(a);
+    case 9: return launch_h16_l<9>(a);
+    case 16: return launch_h16_l<16>(a);
+    default: return fail(RTI_ERR_UNSUPPORTED, "%s: k=%d (supported: 6, 9, 16)", E, k);
   }
 }

@@ -28,12 +28,11 @@
 #include <type_traits>
 
 #include "rti_internal.h"
+#include "rti_stack.h"
 
 namespace rti {
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
 typedef int intx4 __attribute__((ext_vector_type(4)));
 typedef int intx2 __attribute__((ext_vector_type(2)));
 
@@ -1205,30 +1204,21 @@ extern "C" int rti_fit_shared_pm(const float* pinv, int k, int N, const void* I,
                                  int64_t pixel_stride, int64_t channel_stride, float* coef, int coef_layout,
                                  int64_t coef_channel_stride, int kernel, rti_stream_t stream) {
   if (!pm_flags_ok(kernel)) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_pm: unknown kernel bits 0x%x", kernel);
-  if (!pinv || !I || !coef) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_pm: null pointer");
-  if (N <= 0 || P <= 0 || C <= 0 || C > 65535) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_pm: bad N/P/C");
-  if (k < 1 || k > 16) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_pm: k=%d outside 1..16", k);
-  if (N < k) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_pm: N=%d < k=%d", N, k);
-  if (in_dtype != RTI_F32 && in_dtype != RTI_U8 && in_dtype != RTI_I32)
-    return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_pm: input dtype %d", in_dtype);
-  if (coef_layout != RTI_COEF_PIXEL_MAJOR && coef_layout != RTI_COEF_PLANAR)
-    return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_pm: coef layout %d", coef_layout);
-  PmArgs a;
-  a.pinv = pinv;
-  a.k = k;
-  a.N = N;
-  a.I = I;
-  a.P = P;
-  a.C = C;
-  a.ps = pixel_stride ? pixel_stride : N;
-  a.cs = channel_stride ? channel_stride : P * a.ps;
-  a.coef = coef;
-  a.layout = coef_layout;
-  a.ocs = coef_channel_stride ? coef_channel_stride : P * k;
-  a.stream = (hipStream_t)stream;
-  if (a.ps < N) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_pm: pixel_stride < N");
-  if (C > 1 && a.cs < P * a.ps) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_pm: channel_stride");
-  if (C > 1 && a.ocs < P * k) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_pm: coef_channel_stride");
+  const char* const E = "rti_fit_shared_pm";
+  if (int st = check_pointers(E, {pinv, I, coef})) return st;
+  if (int st = check_extents(E, "N/P/C", N, P, C)) return st;
+  if (k < 1 || k > 16) return fail(RTI_ERR_BAD_ARG, "%s: k=%d outside 1..16", E, k);
+  if (int st = check_lights(E, N, k)) return st;
+  if (int st = check_in_dtype(E, in_dtype)) return st;
+  if (int st = check_coef_layout(E, coef_layout)) return st;
+  // the stack is pixel-major here: strides of its own, the coefficient view as everywhere
+  const int64_t ps = pixel_stride ? pixel_stride : N;
+  const CoefView out = coef_view(coef, coef_layout, k, P, coef_channel_stride);
+  const PmArgs a{pinv, k, N, I, P, C, ps, channel_stride ? channel_stride : P * ps, coef, coef_layout, out.ocstride,
+                 (hipStream_t)stream};
+  if (a.ps < N) return fail(RTI_ERR_BAD_ARG, "%s: pixel_stride < N", E);
+  if (C > 1 && a.cs < P * a.ps) return fail(RTI_ERR_BAD_ARG, "%s: channel_stride", E);
+  if (int st = check_coef_stride(E, out, P, C)) return st;
   note_launches(1);
   const int sel = kernel & 0xff;
   const int w_req = (kernel >> RTI_KERNEL_TILE_WAVES_SHIFT) & 0xF, c_req = (kernel >> RTI_KERNEL_CHUNKS_SHIFT) & 0xF;
@@ -1274,11 +1264,7 @@ extern "C" int rti_fit_shared_pm(const float* pinv, int k, int N, const void* I,
     default:
       if (sel == RTI_KERNEL_MFMA || sel == RTI_KERNEL_TILE)
         return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_pm: the DMA/MFMA kernels do not take this shape");
-      switch (in_dtype) {
-        case RTI_F32: launch_lane<float>(a); break;
-        case RTI_I32: launch_lane<int32_t>(a); break;
-        default: launch_lane<uint8_t>(a); break;
-      }
+      with_in_dtype(in_dtype, [&](auto t) { launch_lane<decltype(t)>(a); });
   }
   return st != RTI_OK ? st : check_launch("rti_fit_shared_pm");
 }

@@ -26,14 +26,13 @@
 
 #include "rti_internal.h"
 #include "rti_q8.h"
+#include "rti_stack.h"
 
 namespace rti {
 namespace {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef int v2i __attribute__((ext_vector_type(2)));
-typedef float floatx2 __attribute__((ext_vector_type(2)));
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int Q8_R = 1024;            // tile pixels
 constexpr int Q8_W = 8;               // waves per workgroup
@@ -230,13 +229,8 @@ fit_q8(const unsigned char* __restrict__ op, int N, const unsigned char* __restr
 
 struct Q8Args {
   const unsigned char* op;
-  int k, N;
-  const unsigned char* I;
-  int64_t P, lstride, cstride;
-  int C;
-  float* coef;
-  int layout;
-  int64_t ocstride;
+  StackView in;  // u8
+  CoefView out;
   hipStream_t s;
   int64_t pb = 0, pe = 0;
   int tpw = 1;  // consecutive tiles streamed by one workgroup
@@ -247,30 +241,31 @@ size_t q8_lds_bytes(int N) { return (size_t)q8_operator_bytes(N) + (size_t)2 * Q
 
 template <int K, int LAYOUT>
 int launch_q8_t(const Q8Args& a) {
-  const size_t lds = q8_lds_bytes(a.N);
+  const StackView& in = a.in;
+  const size_t lds = q8_lds_bytes(in.N);
   auto kern = a.stage ? fit_q8<K, LAYOUT, true> : fit_q8<K, LAYOUT, false>;
   if (reserve_lds(reinterpret_cast<const void*>(kern), lds) != hipSuccess)
     return fail(RTI_ERR_HIP, "rti_fit_shared_q8: cannot reserve %zu B of LDS", lds);
-  const int64_t pe = a.pe ? a.pe : a.P;
+  const int64_t pe = a.pe ? a.pe : in.P;
   const int64_t tiles = (pe - a.pb + Q8_R - 1) / Q8_R;
   const int tpw = a.tpw > 0 ? a.tpw : 1;
-  const dim3 grid((unsigned)((tiles + tpw - 1) / tpw), a.C);  // workgroup w streams tiles w, w + G, ...
-  hipLaunchKernelGGL(kern, grid, dim3(64 * Q8_W), lds, a.s, a.op, a.N, a.I, a.pb, pe, tpw, a.P, a.lstride, a.cstride,
-                     a.coef, a.ocstride);
+  const dim3 grid((unsigned)((tiles + tpw - 1) / tpw), in.C);  // workgroup w streams tiles w, w + G, ...
+  hipLaunchKernelGGL(kern, grid, dim3(64 * Q8_W), lds, a.s, a.op, in.N, static_cast<const unsigned char*>(in.I), a.pb, pe,
+                     tpw, in.P, in.lstride, in.cstride, a.out.coef, a.out.ocstride);
   return check_launch("rti_fit_shared_q8");
 }
 
 template <int K>
 int launch_q8_l(const Q8Args& a) {
-  return a.layout == RTI_COEF_PLANAR ? launch_q8_t<K, RTI_COEF_PLANAR>(a) : launch_q8_t<K, RTI_COEF_PIXEL_MAJOR>(a);
+  return a.out.layout == RTI_COEF_PLANAR ? launch_q8_t<K, RTI_COEF_PLANAR>(a) : launch_q8_t<K, RTI_COEF_PIXEL_MAJOR>(a);
 }
 
 int launch_q8(const Q8Args& a) {
-  switch (a.k) {
+  switch (a.out.k) {
     case 6: return launch_q8_l<6>(a);
     case 9: return launch_q8_l<9>(a);
     case 16: return launch_q8_l<16>(a);
-    default: return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_q8: k=%d (supported: 6, 9, 16)", a.k);
+    default: return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_q8: k=%d (supported: 6, 9, 16)", a.out.k);
   }
 }
 
@@ -290,33 +285,20 @@ extern "C" int rti_fit_shared_q8(const void* op, int k, int N, const uint8_t* I,
                                  int64_t coef_channel_stride, int kernel, rti_stream_t stream) {
   if (!kernel_bits_ok(kernel, RTI_KERNEL_AUTO, RTI_KERNEL_STAGE | RTI_FIELD_CHUNKS | RTI_FIELD_TILE_DEPTH))
     return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_q8: unknown kernel bits 0x%x", kernel);
-  if (!op || !I || !coef) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_q8: null pointer");
-  if (N <= 0 || P <= 0 || C <= 0 || C > 65535) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_q8: bad N/P/C");
-  if (N < k) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_q8: N=%d < k=%d", N, k);
-  if (coef_layout != RTI_COEF_PIXEL_MAJOR && coef_layout != RTI_COEF_PLANAR)
-    return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_q8: coef layout %d", coef_layout);
+  const char* const E = "rti_fit_shared_q8";
+  if (int st = check_pointers(E, {op, I, coef})) return st;
+  if (int st = check_extents(E, "N/P/C", N, P, C)) return st;
+  if (int st = check_lights(E, N, k)) return st;
+  if (int st = check_coef_layout(E, coef_layout)) return st;
   if (N > rti_fit_shared_q8_max_lights())
-    return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_q8: N=%d > %d (LDS)", N, rti_fit_shared_q8_max_lights());
-  Q8Args a;
-  a.op = static_cast<const unsigned char*>(op);
-  a.k = k;
-  a.N = N;
-  a.I = I;
-  a.P = P;
-  a.C = C;
-  a.lstride = light_stride ? light_stride : P;
-  a.cstride = channel_stride ? channel_stride : (int64_t)N * a.lstride;
-  a.coef = coef;
-  a.layout = coef_layout;
-  a.ocstride = coef_channel_stride ? coef_channel_stride : P * k;
-  a.s = (hipStream_t)stream;
-  if (a.lstride < P) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_q8: light_stride < P");
-  if (C > 1 && a.cstride < (int64_t)N * a.lstride) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_q8: channel_stride");
-  if (C > 1 && a.ocstride < P * k) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_q8: coef_channel_stride");
+    return fail(RTI_ERR_UNSUPPORTED, "%s: N=%d > %d (LDS)", E, N, rti_fit_shared_q8_max_lights());
+  Q8Args a{static_cast<const unsigned char*>(op), stack_view(I, RTI_U8, N, P, C, light_stride, channel_stride),
+           coef_view(coef, coef_layout, k, P, coef_channel_stride), (hipStream_t)stream};
+  if (int st = check_stack_strides(E, a.in)) return st;
+  if (int st = check_coef_stride(E, a.out, P, C)) return st;
   // 16-byte lane loads of 16 pixels; coefficient rows stored as float2/float4 where k allows
-  if (P % 16 || a.lstride % 16 || a.cstride % 16 || !aligned_to(I, 16) || !aligned_to(op, 16) ||
-      !aligned_to(coef, 16) || a.ocstride % 4)
-    return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_q8: needs P, strides and pointers 16-byte aligned");
+  if (!stack_vec_ok_any_c(a.in, 16) || !aligned_to(op, 16) || !coef_vec_ok_any_c(a.out))
+    return fail(RTI_ERR_UNSUPPORTED, "%s: needs P, strides and pointers 16-byte aligned", E);
   note_launches(1);
   // One workgroup per CU (146 KiB of LDS), every workgroup streaming tpw tiles (interleaved with the other
   // workgroups') through its load pipeline: a tile of 1024 pixels x N <= 448 lights is only 2-7 steps, and

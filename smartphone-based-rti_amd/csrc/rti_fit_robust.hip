@@ -35,6 +35,7 @@
 #include <cstdint>
 
 #include "rti_internal.h"
+#include "rti_stack.h"
 
 namespace rti {
 namespace {
@@ -276,17 +277,11 @@ fit_robust_k(const double* __restrict__ A, int N, const T* __restrict__ I, int64
 
 struct RbArgs {
   const double* A;
-  int k, N;
-  const void* I;
-  int in_dtype;
-  int64_t P, lstride, cstride;
-  int C;
+  StackView in;
   double lo, hi;
   int min_lights, iters;
   double delta;
-  float* coef;
-  int layout;
-  int64_t ocstride;
+  CoefView out;
   float* res;
   int32_t* kept;
   int* fallback_px;
@@ -298,12 +293,14 @@ struct RbArgs {
 template <int K, typename T, int TP, bool RESIDENT, bool ITER, int LAYOUT>
 int launch_rb(const RbArgs& a) {
   auto kern = fit_robust_k<K, T, TP, RESIDENT, ITER, LAYOUT>;
-  const size_t lds = RESIDENT ? (size_t)a.N * TP * sizeof(T) : 0;
+  const StackView& in = a.in;
+  const size_t lds = RESIDENT ? (size_t)in.N * TP * sizeof(T) : 0;
   if (lds > 64 * 1024 && reserve_lds(reinterpret_cast<const void*>(kern), lds) != hipSuccess)
     return fail(RTI_ERR_HIP, "rti_fit_shared_robust: cannot reserve %zu bytes of LDS", lds);
-  const dim3 grid(grid_1d(a.P, TP), a.C);
-  hipLaunchKernelGGL(kern, grid, dim3(TP), lds, a.s, a.A, a.N, static_cast<const T*>(a.I), a.P, a.lstride, a.cstride,
-                     a.lo, a.hi, a.min_lights, a.iters, a.delta, a.coef, a.ocstride, a.res, a.kept, a.fallback_px, a.vec);
+  const dim3 grid(grid_1d(in.P, TP), in.C);
+  hipLaunchKernelGGL(kern, grid, dim3(TP), lds, a.s, a.A, in.N, static_cast<const T*>(in.I), in.P, in.lstride, in.cstride,
+                     a.lo, a.hi, a.min_lights, a.iters, a.delta, a.out.coef, a.out.ocstride, a.res, a.kept, a.fallback_px,
+                     a.vec);
   return check_launch("rti_fit_shared_robust");
 }
 
@@ -321,13 +318,13 @@ int launch_rb_form(const RbArgs& a) {
 
 template <int K, typename T>
 int launch_rb_l(const RbArgs& a) {
-  return a.layout == RTI_COEF_PLANAR ? launch_rb_form<K, T, RTI_COEF_PLANAR>(a)
+  return a.out.layout == RTI_COEF_PLANAR ? launch_rb_form<K, T, RTI_COEF_PLANAR>(a)
                                      : launch_rb_form<K, T, RTI_COEF_PIXEL_MAJOR>(a);
 }
 
 template <typename T>
 int launch_rb_k(const RbArgs& a) {
-  return a.k == 6 ? launch_rb_l<6, T>(a) : launch_rb_l<9, T>(a);
+  return a.out.k == 6 ? launch_rb_l<6, T>(a) : launch_rb_l<9, T>(a);
 }
 
 int rb_elem_size(int in_dtype) { return in_dtype == RTI_U8 ? 1 : 4; }
@@ -352,51 +349,30 @@ extern "C" int rti_fit_shared_robust(const double* A, int k, int N, const void* 
                                      int kernel, rti_stream_t stream) {
   if (!kernel_bits_ok(kernel, RTI_KERNEL_AUTO, RTI_KERNEL_ONE_LAUNCH))
     return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: unknown kernel bits 0x%x", kernel);
-  if (!A || !I || !coef) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: null pointer");
-  if (N <= 0 || P <= 0 || C <= 0 || C > 65535) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: bad N/P/C");
-  if (k == 16)
-    return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_robust: k=16 (its 136 + 16 fp64 accumulators do not fit one lane)");
-  if (k != 6 && k != 9) return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_robust: k=%d (supported: 6, 9)", k);
-  if (in_dtype != RTI_F32 && in_dtype != RTI_U8 && in_dtype != RTI_I32)
-    return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_robust: input dtype %d", in_dtype);
-  if (N < k) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: N=%d < k=%d", N, k);
-  if (!(lo <= hi)) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: window needs lo <= hi, neither NaN");
+  const char* const E = "rti_fit_shared_robust";
+  if (int st = check_pointers(E, {A, I, coef})) return st;
+  if (int st = check_extents(E, "N/P/C", N, P, C)) return st;
+  if (k == 16) return fail(RTI_ERR_UNSUPPORTED, "%s: k=16 (its 136 + 16 fp64 accumulators do not fit one lane)", E);
+  if (k != 6 && k != 9) return fail(RTI_ERR_UNSUPPORTED, "%s: k=%d (supported: 6, 9)", E, k);
+  if (int st = check_in_dtype(E, in_dtype)) return st;
+  if (int st = check_lights(E, N, k)) return st;
+  if (!(lo <= hi)) return fail(RTI_ERR_BAD_ARG, "%s: window needs lo <= hi, neither NaN", E);
   if (min_lights < k || min_lights > N)
-    return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: min_lights=%d outside [k=%d, N=%d]", min_lights, k, N);
-  if (iters < 0 || iters > 16) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: iters=%d outside [0, 16]", iters);
-  if (iters > 0 && !(delta > 0.0f)) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: delta must be > 0");
-  if (coef_layout != RTI_COEF_PIXEL_MAJOR && coef_layout != RTI_COEF_PLANAR)
-    return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: coef layout %d", coef_layout);
-  RbArgs a;
-  a.A = A;
-  a.k = k;
-  a.N = N;
-  a.I = I;
-  a.in_dtype = in_dtype;
-  a.P = P;
-  a.C = C;
-  a.lstride = light_stride ? light_stride : P;
-  a.cstride = channel_stride ? channel_stride : (int64_t)N * a.lstride;
-  a.lo = (double)lo;
-  a.hi = (double)hi;
-  a.min_lights = min_lights;
-  a.iters = iters;
-  a.delta = (double)delta;
-  a.coef = coef;
-  a.layout = coef_layout;
-  a.ocstride = coef_channel_stride ? coef_channel_stride : P * k;
-  a.res = res;
-  a.kept = kept;
-  a.fallback_px = fallback_px;
-  a.s = (hipStream_t)stream;
-  if (a.lstride < P) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: light_stride < P");
-  if (C > 1 && a.cstride < (int64_t)N * a.lstride) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: channel_stride");
-  if (C > 1 && a.ocstride < P * k) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_robust: coef_channel_stride");
+    return fail(RTI_ERR_BAD_ARG, "%s: min_lights=%d outside [k=%d, N=%d]", E, min_lights, k, N);
+  if (iters < 0 || iters > 16) return fail(RTI_ERR_BAD_ARG, "%s: iters=%d outside [0, 16]", E, iters);
+  if (iters > 0 && !(delta > 0.0f)) return fail(RTI_ERR_BAD_ARG, "%s: delta must be > 0", E);
+  if (int st = check_coef_layout(E, coef_layout)) return st;
+  RbArgs a{A, stack_view(I, in_dtype, N, P, C, light_stride, channel_stride), (double)lo, (double)hi, min_lights, iters,
+           (double)delta, coef_view(coef, coef_layout, k, P, coef_channel_stride), res, kept, fallback_px};
+  if (int st = check_stack_strides(E, a.in)) return st;
+  if (int st = check_coef_stride(E, a.out, P, C)) return st;
   a.tp = rti_fit_shared_robust_plan(k, N, in_dtype, iters, kernel);
-  const int64_t es = rb_elem_size(in_dtype);
-  a.vec = aligned_to(I, 16) && a.lstride * es % 16 == 0 && a.cstride * es % 16 == 0;
+  // 16-byte tile loads, a rule of this kernel's own: strides in bytes, no condition on P
+  const int64_t es = (int64_t)a.in.es;
+  a.vec = aligned_to(I, 16) && a.in.lstride * es % 16 == 0 && a.in.cstride * es % 16 == 0;
+  a.s = (hipStream_t)stream;
   note_launches(1);
-  switch (in_dtype) {
+  switch (in_dtype) {  // not with_in_dtype: its order of instantiation would reorder this file's kernels
     case RTI_F32: return launch_rb_k<float>(a);
     case RTI_U8: return launch_rb_k<uint8_t>(a);
     default: return launch_rb_k<int32_t>(a);

@@ -37,31 +37,13 @@
 #include <cmath>
 #include <cstdint>
 
-#include "rti_internal.h"
+#include "rti_lsq.h"
+#include "rti_stack.h"
 
 namespace rti {
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 constexpr int FR_THREADS = 256;
-
-template <typename T, int VEC>
-__device__ __forceinline__ void load_nt(const T* __restrict__ p, float (&x)[VEC]) {
-  if constexpr (VEC == 1) {
-    x[0] = (float)__builtin_nontemporal_load(p);
-  } else {
-    typedef T vec_t __attribute__((ext_vector_type(VEC)));
-    const vec_t v = __builtin_nontemporal_load(reinterpret_cast<const vec_t*>(p));
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) x[i] = (float)v[i];
-  }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // pixel-major coefficient rows leave through LDS as whole 1 KiB rows per store instruction
 template <int K, int VEC>
@@ -95,7 +77,7 @@ __device__ __forceinline__ double fitres_body(const double* __restrict__ A, cons
 #pragma unroll
     for (int u = 0; u < UP; ++u)
 #pragma unroll
-      for (int c = 0; c < NC; ++c) load_nt<T, VEC>(src + (int64_t)(n + u) * lstride + off[c], x[u][c]);
+      for (int c = 0; c < NC; ++c) load_nt<float>(src + (int64_t)(n + u) * lstride + off[c], x[u][c]);
 #pragma unroll
     for (int u = 0; u < UP; ++u) {
       const double* An = A + (int64_t)(n + u) * K;  // wave-uniform row -> SGPR pairs
@@ -114,7 +96,7 @@ __device__ __forceinline__ double fitres_body(const double* __restrict__ A, cons
   for (; n < N; ++n) {
     float x[NC][VEC];
 #pragma unroll
-    for (int c = 0; c < NC; ++c) load_nt<T, VEC>(src + (int64_t)n * lstride + off[c], x[c]);
+    for (int c = 0; c < NC; ++c) load_nt<float>(src + (int64_t)n * lstride + off[c], x[c]);
     const double* An = A + (int64_t)n * K;
 #pragma unroll
     for (int c = 0; c < NC; ++c)
@@ -237,31 +219,27 @@ fit_shared_residual_k(const double* __restrict__ A, const double* __restrict__ G
 
 struct FrArgs {
   const double *A, *G;
-  int k, N;
-  const void* I;
-  int64_t P, lstride, cstride;
-  int C;
-  float* coef;
-  int layout;
-  int64_t ocstride;
+  int orth;  // (A, G) = (U, V Σ⁻¹): ss = q − yᵀy
+  StackView in;
+  CoefView out;
   float* res;
   double* partial;
-  int nc;
-  int orth = 0;  // (A, G) = (U, V Σ⁻¹): ss = q − yᵀy
   hipStream_t s;
+  int nc = 0;
   int64_t pb = 0, pe = 0;  // this launch's pixel range [pb, pe) (pe 0 = P); pb a multiple of the workgroup span
 };
 
 template <int K, int VEC, int NC, typename T, int LAYOUT>
 int launch_fr_t(const FrArgs& a) {
   constexpr int U = 4;  // loads in flight per lane: the fp64 work per load hides more latency than fp32
-  const int64_t pe = a.pe ? a.pe : a.P;
-  const dim3 grid(grid_1d(pe - a.pb, FR_THREADS * VEC * NC), a.C);
+  const StackView& in = a.in;
+  const int64_t pe = a.pe ? a.pe : in.P;
+  const dim3 grid(grid_1d(pe - a.pb, FR_THREADS * VEC * NC), in.C);
   const size_t lds =
       (LAYOUT == RTI_COEF_PIXEL_MAJOR && fr_stage<K, VEC>()) ? (size_t)FR_THREADS * VEC * K * sizeof(float) : 0;
   hipLaunchKernelGGL((fit_shared_residual_k<K, VEC, NC, U, T, LAYOUT>), grid, dim3(FR_THREADS), lds, a.s, a.A, a.G,
-                     a.N, a.orth, static_cast<const T*>(a.I), a.P, a.pb, pe, a.lstride, a.cstride, a.coef, a.ocstride, a.res, a.partial,
-                     (int64_t)grid_1d(a.P, FR_THREADS));
+                     in.N, a.orth, static_cast<const T*>(in.I), in.P, a.pb, pe, in.lstride, in.cstride, a.out.coef,
+                     a.out.ocstride, a.res, a.partial, (int64_t)grid_1d(in.P, FR_THREADS));
   return check_launch("rti_fit_shared_residual");
 }
 
@@ -280,7 +258,7 @@ int launch_fr_nc(const FrArgs& a) {
 
 template <int K, int VEC, typename T>
 int launch_fr_l(const FrArgs& a) {
-  return a.layout == RTI_COEF_PLANAR ? launch_fr_nc<K, VEC, T, RTI_COEF_PLANAR>(a)
+  return a.out.layout == RTI_COEF_PLANAR ? launch_fr_nc<K, VEC, T, RTI_COEF_PLANAR>(a)
                                      : launch_fr_nc<K, VEC, T, RTI_COEF_PIXEL_MAJOR>(a);
 }
 
@@ -291,11 +269,11 @@ int launch_fr_v(const FrArgs& a, bool vec4) {
 
 template <typename T>
 int launch_fr_k(const FrArgs& a, bool vec4) {
-  switch (a.k) {
+  switch (a.out.k) {
     case 6: return launch_fr_v<6, T>(a, vec4);
     case 9: return launch_fr_v<9, T>(a, vec4);
     case 16: return launch_fr_v<16, T>(a, vec4);
-    default: return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_residual: k=%d (supported: 6, 9, 16)", a.k);
+    default: return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_residual: k=%d (supported: 6, 9, 16)", a.out.k);
   }
 }
 
@@ -319,40 +297,21 @@ int fit_shared_residual_impl(bool orth, const double* A, const double* ginv, int
                              int64_t P, int C, int64_t light_stride, int64_t channel_stride, float* coef,
                              int coef_layout, int64_t coef_channel_stride, float* res, double* partial, int kernel,
                              rti_stream_t stream) {
+  const char* const E = "rti_fit_shared_residual";  // both entries report under this name
   if (!kernel_bits_ok(kernel, RTI_KERNEL_AUTO, RTI_KERNEL_ONE_LAUNCH | RTI_FIELD_CHUNKS))
-    return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_residual: unknown kernel bits 0x%x", kernel);
-  if (!A || !ginv || !I || !coef) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_residual: null pointer");
-  if (N <= 0 || P <= 0 || C <= 0 || C > 65535) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_residual: bad N/P/C");
-  if (N < k) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_residual: N=%d < k=%d", N, k);
-  if (in_dtype != RTI_F32 && in_dtype != RTI_U8 && in_dtype != RTI_I32)
-    return fail(RTI_ERR_UNSUPPORTED, "rti_fit_shared_residual: input dtype %d", in_dtype);
-  if (coef_layout != RTI_COEF_PIXEL_MAJOR && coef_layout != RTI_COEF_PLANAR)
-    return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_residual: coef layout %d", coef_layout);
+    return fail(RTI_ERR_BAD_ARG, "%s: unknown kernel bits 0x%x", E, kernel);
+  if (int st = check_pointers(E, {A, ginv, I, coef})) return st;
+  if (int st = check_extents(E, "N/P/C", N, P, C)) return st;
+  if (int st = check_lights(E, N, k)) return st;
+  if (int st = check_in_dtype(E, in_dtype)) return st;
+  if (int st = check_coef_layout(E, coef_layout)) return st;
   note_launches(1);
-  FrArgs a;
-  a.A = A;
-  a.G = ginv;
-  a.k = k;
-  a.N = N;
-  a.I = I;
-  a.P = P;
-  a.C = C;
-  a.lstride = light_stride ? light_stride : P;
-  a.cstride = channel_stride ? channel_stride : (int64_t)N * a.lstride;
-  a.coef = coef;
-  a.layout = coef_layout;
-  a.ocstride = coef_channel_stride ? coef_channel_stride : P * k;
-  a.res = res;
-  a.partial = partial;
-  a.orth = orth ? 1 : 0;
-  a.s = (hipStream_t)stream;
-  if (a.lstride < P) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_residual: light_stride < P");
-  if (C > 1 && a.cstride < (int64_t)N * a.lstride)
-    return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_residual: channel_stride");
-  if (C > 1 && a.ocstride < P * k) return fail(RTI_ERR_BAD_ARG, "rti_fit_shared_residual: coef_channel_stride");
-  const size_t es = in_dtype == RTI_U8 ? 1 : 4;
-  const bool vec4 = P % 4 == 0 && a.lstride % 4 == 0 && a.cstride % 4 == 0 && aligned_to(I, 4 * es) &&
-                    (!res || aligned_to(res, 16)) && aligned_to(coef, 16) && a.ocstride % 4 == 0;
+  FrArgs a{A, ginv, orth ? 1 : 0, stack_view(I, in_dtype, N, P, C, light_stride, channel_stride),
+           coef_view(coef, coef_layout, k, P, coef_channel_stride), res, partial, (hipStream_t)stream};
+  if (int st = check_stack_strides(E, a.in)) return st;
+  if (int st = check_coef_stride(E, a.out, P, C)) return st;
+  const size_t es = a.in.es;
+  const bool vec4 = stack_vec_ok_any_c(a.in, 4) && (!res || aligned_to(res, 16)) && coef_vec_ok_any_c(a.out);
   a.nc = (kernel >> RTI_KERNEL_CHUNKS_SHIFT) & 0xF;
   // launch generations (rti_fit.hip): PTM-6 on 16-B lanes as consecutive launches over pixel ranges of
   // whole workgroups, each giving the SIMDs one or two waves (3 or 2 chunks per lane: 205 / <= 160
@@ -394,20 +353,16 @@ int fit_shared_residual_impl(bool orth, const double* A, const double* ginv, int
         }
   }
   auto launch = [&](const FrArgs& b) {
-    switch (in_dtype) {
-      case RTI_F32: return launch_fr_k<float>(b, vec4);
-      case RTI_U8: return launch_fr_k<uint8_t>(b, vec4);
-      default: return launch_fr_k<int32_t>(b, vec4);
-    }
+    return with_in_dtype(in_dtype, [&](auto t) { return launch_fr_k<decltype(t)>(b, vec4); });
   };
   if (parts == 1) return launch(a);
   const int64_t span = (int64_t)FR_THREADS * 4 * a.nc, units = (P + span - 1) / span;
   const int64_t per = (units + parts - 1) / parts, pstride = rti_fit_shared_residual_blocks(P);
   for (int c = 0; c < C; ++c) {
     FrArgs b = a;
-    b.C = 1;
-    b.I = static_cast<const char*>(I) + (size_t)c * a.cstride * es;
-    b.coef = coef + (size_t)c * a.ocstride;
+    b.in.C = 1;
+    b.in.I = static_cast<const char*>(I) + (size_t)c * a.in.cstride * es;
+    b.out.coef = coef + (size_t)c * a.out.ocstride;
     b.res = res ? res + (size_t)c * P : nullptr;
     b.partial = partial ? partial + (size_t)c * pstride : nullptr;
     for (int i = 0; i < parts; ++i) {

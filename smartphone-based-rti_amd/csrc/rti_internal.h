@@ -10,6 +10,9 @@
 
 namespace rti {
 
+typedef float floatx2 __attribute__((ext_vector_type(2)));
+typedef float floatx4 __attribute__((ext_vector_type(4)));
+
 // Records a thread-local message (rti_last_error) and returns `status`.
 int fail(int status, const char* fmt, ...);
 // hipGetLastError after a launch -> RTI_OK or RTI_ERR_HIP.

@@ -28,11 +28,10 @@
 
 #include "rti_convert.h"
 #include "rti_internal.h"
+#include "rti_stack.h"
 
 namespace rti {
 namespace {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
 
 constexpr int TILE_P = 64;    // pixels per workgroup tile
 constexpr int ROWS_WG = 256;  // operator rows per workgroup sweep step (4 waves × 64)
@@ -452,28 +451,24 @@ extern "C" int rti_apply_operator(const float* opT, int E, int N, int64_t op_str
                                   int64_t P, int C, int64_t light_stride, int64_t channel_stride, void* out,
                                   int out_dtype, int64_t out_row_stride, int64_t out_channel_stride,
                                   rti_stream_t stream) {
-  if (!opT || !I || !out) return fail(RTI_ERR_BAD_ARG, "rti_apply_operator: null pointer");
-  if (E <= 0 || N <= 0 || P <= 0 || C <= 0 || C > 65535)
-    return fail(RTI_ERR_BAD_ARG, "rti_apply_operator: bad E/N/P/C");
-  if (in_dtype != RTI_F32 && in_dtype != RTI_U8 && in_dtype != RTI_I32)
-    return fail(RTI_ERR_UNSUPPORTED, "rti_apply_operator: input dtype %d", in_dtype);
+  const char* const En = "rti_apply_operator";
+  if (int st = check_pointers(En, {opT, I, out})) return st;
+  if (E <= 0 || !extents_ok(N, P, C)) return fail(RTI_ERR_BAD_ARG, "%s: bad E/N/P/C", En);
+  if (int st = check_in_dtype(En, in_dtype)) return st;
   if (out_dtype != RTI_F32 && out_dtype != RTI_F64 && out_dtype != RTI_I32 && out_dtype != RTI_U8)
-    return fail(RTI_ERR_UNSUPPORTED, "rti_apply_operator: out dtype %d", out_dtype);
+    return fail(RTI_ERR_UNSUPPORTED, "%s: out dtype %d", En, out_dtype);
+  const StackView in = stack_view(I, in_dtype, N, P, C, light_stride, channel_stride);
   const int64_t os = op_stride ? op_stride : E;
-  const int64_t ls = light_stride ? light_stride : P;
-  const int64_t cs = channel_stride ? channel_stride : (int64_t)N * ls;
   const int64_t orow = out_row_stride ? out_row_stride : P;
   const int64_t ocs = out_channel_stride ? out_channel_stride : (int64_t)E * orow;
-  if (os < E || ls < P || orow < P) return fail(RTI_ERR_BAD_ARG, "rti_apply_operator: stride smaller than extent");
-  const size_t ie = esize(in_dtype), oe = esize(out_dtype);
-  const bool vec = os % 4 == 0 && aligned_to(opT, 16) && P % 4 == 0 && ls % 4 == 0 && cs % 4 == 0 &&
-                   aligned_to(I, 4 * ie) && orow % 4 == 0 && ocs % 4 == 0 && aligned_to(out, 4 * oe);
-  hipStream_t s = (hipStream_t)stream;
-  switch (in_dtype) {
-    case RTI_F32: return launch_out<float>(out_dtype, opT, E, N, os, I, P, C, ls, cs, out, orow, ocs, vec, s);
-    case RTI_I32: return launch_out<int32_t>(out_dtype, opT, E, N, os, I, P, C, ls, cs, out, orow, ocs, vec, s);
-    default: return launch_out<uint8_t>(out_dtype, opT, E, N, os, I, P, C, ls, cs, out, orow, ocs, vec, s);
-  }
+  // the operator entries have never checked a channel stride: only the extents of a row
+  if (os < E || in.lstride < P || orow < P) return fail(RTI_ERR_BAD_ARG, "%s: stride smaller than extent", En);
+  const bool vec = os % 4 == 0 && aligned_to(opT, 16) && stack_vec_ok_any_c(in, 4) && orow % 4 == 0 && ocs % 4 == 0 &&
+                   aligned_to(out, 4 * esize(out_dtype));
+  return with_in_dtype(in_dtype, [&](auto t) {
+    return launch_out<decltype(t)>(out_dtype, opT, E, N, os, I, P, C, in.lstride, in.cstride, out, orow, ocs, vec,
+                                   (hipStream_t)stream);
+  });
 }
 
 extern "C" int rti_operator_split_f16(const double* opT, int N, int E, int64_t op_stride, int Kp, uint16_t* hi,
@@ -510,33 +505,25 @@ extern "C" int rti_apply_operator_f16(const uint16_t* op_hi, const uint16_t* op_
                                       int N, const void* I, int in_dtype, int64_t P, int C, int64_t light_stride,
                                       int64_t channel_stride, void* out, int out_dtype, int64_t out_row_stride,
                                       int64_t out_channel_stride, rti_stream_t stream) {
-  if (!op_hi || !op_lo || !I || !out) return fail(RTI_ERR_BAD_ARG, "rti_apply_operator_f16: null pointer");
-  if (E <= 0 || N <= 0 || P <= 0 || C <= 0 || C > 65535)
-    return fail(RTI_ERR_BAD_ARG, "rti_apply_operator_f16: bad E/N/P/C");
-  if (Kp < N || Kp % 16 != 0) return fail(RTI_ERR_BAD_ARG, "rti_apply_operator_f16: Kp must be a multiple of 16 >= N");
-  if (Kp > 256) return fail(RTI_ERR_UNSUPPORTED, "rti_apply_operator_f16: N=%d > 256 lights", N);
-  if (in_dtype != RTI_F32 && in_dtype != RTI_U8 && in_dtype != RTI_I32)
-    return fail(RTI_ERR_UNSUPPORTED, "rti_apply_operator_f16: input dtype %d", in_dtype);
+  const char* const En = "rti_apply_operator_f16";
+  if (int st = check_pointers(En, {op_hi, op_lo, I, out})) return st;
+  if (E <= 0 || !extents_ok(N, P, C)) return fail(RTI_ERR_BAD_ARG, "%s: bad E/N/P/C", En);
+  if (Kp < N || Kp % 16 != 0) return fail(RTI_ERR_BAD_ARG, "%s: Kp must be a multiple of 16 >= N", En);
+  if (Kp > 256) return fail(RTI_ERR_UNSUPPORTED, "%s: N=%d > 256 lights", En, N);
+  if (int st = check_in_dtype(En, in_dtype)) return st;
   if (out_dtype != RTI_F32 && out_dtype != RTI_F64 && out_dtype != RTI_I32 && out_dtype != RTI_U8)
-    return fail(RTI_ERR_UNSUPPORTED, "rti_apply_operator_f16: out dtype %d", out_dtype);
+    return fail(RTI_ERR_UNSUPPORTED, "%s: out dtype %d", En, out_dtype);
   if (!aligned_to(op_hi, 16) || !aligned_to(op_lo, 16))
-    return fail(RTI_ERR_BAD_ARG, "rti_apply_operator_f16: operator halves must be 16-byte aligned");
-  const int64_t ls = light_stride ? light_stride : P;
-  const int64_t cs = channel_stride ? channel_stride : (int64_t)N * ls;
+    return fail(RTI_ERR_BAD_ARG, "%s: operator halves must be 16-byte aligned", En);
+  const StackView in = stack_view(I, in_dtype, N, P, C, light_stride, channel_stride);
   const int64_t orow = out_row_stride ? out_row_stride : P;
   const int64_t ocs = out_channel_stride ? out_channel_stride : (int64_t)E * orow;
-  if (ls < P || orow < P) return fail(RTI_ERR_BAD_ARG, "rti_apply_operator_f16: stride smaller than extent");
-  const size_t ie = esize(in_dtype);
-  const bool vec = P % 4 == 0 && ls % 4 == 0 && cs % 4 == 0 && aligned_to(I, 4 * ie);
+  if (in.lstride < P || orow < P) return fail(RTI_ERR_BAD_ARG, "%s: stride smaller than extent", En);
+  const bool vec = stack_vec_ok_any_c(in, 4);
   const _Float16* hi = reinterpret_cast<const _Float16*>(op_hi);
   const _Float16* lo = reinterpret_cast<const _Float16*>(op_lo);
-  hipStream_t s = (hipStream_t)stream;
-  switch (in_dtype) {
-    case RTI_F32:
-      return launch_f16_out<float>(out_dtype, hi, lo, Kp, inv_scale, E, N, I, P, C, ls, cs, out, orow, ocs, vec, s);
-    case RTI_I32:
-      return launch_f16_out<int32_t>(out_dtype, hi, lo, Kp, inv_scale, E, N, I, P, C, ls, cs, out, orow, ocs, vec, s);
-    default:
-      return launch_f16_out<uint8_t>(out_dtype, hi, lo, Kp, inv_scale, E, N, I, P, C, ls, cs, out, orow, ocs, vec, s);
-  }
+  return with_in_dtype(in_dtype, [&](auto t) {
+    return launch_f16_out<decltype(t)>(out_dtype, hi, lo, Kp, inv_scale, E, N, I, P, C, in.lstride, in.cstride, out, orow, ocs,
+                                       vec, (hipStream_t)stream);
+  });
 }

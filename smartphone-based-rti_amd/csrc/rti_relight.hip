@@ -51,8 +51,6 @@ __device__ __forceinline__ float dot_k(const float (&c)[K], const float* b) {
   return acc;
 }
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-
 // Pixel-major coefficient rows through LDS.  A lane's own 4 pixels are K·sizeof(TC)·4 contiguous
 // bytes, so per-lane loads stride that far across the wave (96 B for PTM-6 fp32) and every
 // 128-B line is requested by several load instructions.  Instead the wave reads its 256 pixels'

@@ -21,30 +21,13 @@
 #include <cmath>
 #include <cstdint>
 
-#include "rti_internal.h"
+#include "rti_lsq.h"
+#include "rti_stack.h"
 
 namespace rti {
 namespace {
 
 constexpr int RES_THREADS = 256;
-
-template <typename T, int VEC>
-__device__ __forceinline__ void load_vec(const T* __restrict__ p, float (&x)[VEC]) {
-  if constexpr (VEC == 1) {
-    x[0] = (float)__builtin_nontemporal_load(p);
-  } else {
-    typedef T vec_t __attribute__((ext_vector_type(VEC)));
-    const vec_t v = __builtin_nontemporal_load(reinterpret_cast<const vec_t*>(p));
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) x[i] = (float)v[i];
-  }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // Wide lanes (as the fit): a wave owns NC·64·VEC consecutive pixels and
 // lane l's chunk j is the VEC pixels at wave_base + j·64·VEC + VEC·l, so the wave's NC loads
@@ -78,7 +61,7 @@ __global__ __launch_bounds__(RES_THREADS) void fit_residual_k(const float* __res
 #pragma unroll
       for (int i = 0; i < K; ++i) {
         float x[VEC];
-        load_vec<float, VEC>(cc + i * P + p0, x);
+        load_nt<float>(cc + i * P + p0, x);
 #pragma unroll
         for (int v = 0; v < VEC; ++v) a[j][v][i] = x[v];
       }
@@ -89,7 +72,7 @@ __global__ __launch_bounds__(RES_THREADS) void fit_residual_k(const float* __res
     float x[NC][VEC];
 #pragma unroll
     for (int j = 0; j < NC; ++j)
-      if (live[j]) load_vec<T, VEC>(Ic + n * lstride + base + j * 64 * VEC, x[j]);
+      if (live[j]) load_nt<float>(Ic + n * lstride + base + j * 64 * VEC, x[j]);
     const float* An = A + (int64_t)n * K;  // wave-uniform row
 #pragma unroll
     for (int j = 0; j < NC; ++j) {
@@ -137,24 +120,20 @@ __global__ __launch_bounds__(RES_THREADS) void fit_residual_k(const float* __res
 
 struct ResArgs {
   const float* A;
-  int k, N;
-  const void* I;
-  int64_t P, lstride, cstride;
-  const float* coef;
-  int layout;
-  int64_t ocstride;
+  StackView in;
+  CoefSource coef;  // read here
   float* res;
   double* partial;
-  int C;
   hipStream_t s;
 };
 
 template <int K, int VEC, int NC, typename T>
 int launch_res(const ResArgs& a) {
-  const dim3 grid(grid_1d(a.P, RES_THREADS * VEC * NC), a.C);
-  hipLaunchKernelGGL((fit_residual_k<K, VEC, NC, T>), grid, dim3(RES_THREADS), 0, a.s, a.A, a.N,
-                     static_cast<const T*>(a.I), a.P, a.lstride, a.cstride, a.coef, a.layout, a.ocstride, a.res,
-                     a.partial, (int64_t)grid_1d(a.P, RES_THREADS));
+  const StackView& in = a.in;
+  const dim3 grid(grid_1d(in.P, RES_THREADS * VEC * NC), in.C);
+  hipLaunchKernelGGL((fit_residual_k<K, VEC, NC, T>), grid, dim3(RES_THREADS), 0, a.s, a.A, in.N,
+                     static_cast<const T*>(in.I), in.P, in.lstride, in.cstride, a.coef.coef, a.coef.layout, a.coef.ocstride,
+                     a.res, a.partial, (int64_t)grid_1d(in.P, RES_THREADS));
   return check_launch("rti_fit_residual");
 }
 
@@ -170,18 +149,18 @@ int launch_res_v(const ResArgs& a, bool vec4) {
   if (!vec4) return launch_res<K, 1, 1, T>(a);
   if constexpr (K == 6) {
     constexpr int NC = 4;
-    if (a.P * a.C / (64 * 4 * NC) >= kResWideMinWaves) return launch_res<K, 4, NC, T>(a);
+    if (a.in.P * a.in.C / (64 * 4 * NC) >= kResWideMinWaves) return launch_res<K, 4, NC, T>(a);
   }
   return launch_res<K, 4, 1, T>(a);
 }
 
 template <typename T>
 int launch_res_k(const ResArgs& a, bool vec4) {
-  switch (a.k) {
+  switch (a.coef.k) {
     case 6: return launch_res_v<6, T>(a, vec4);
     case 9: return launch_res_v<9, T>(a, vec4);
     case 16: return launch_res_v<16, T>(a, vec4);
-    default: return fail(RTI_ERR_UNSUPPORTED, "rti_fit_residual: k=%d (supported: 6, 9, 16)", a.k);
+    default: return fail(RTI_ERR_UNSUPPORTED, "rti_fit_residual: k=%d (supported: 6, 9, 16)", a.coef.k);
   }
 }
 
@@ -200,37 +179,17 @@ extern "C" int64_t rti_fit_residual_blocks(int64_t P) {
 extern "C" int rti_fit_residual(const float* A, int k, int N, const void* I, int in_dtype, int64_t P, int C,
                                 int64_t light_stride, int64_t channel_stride, const float* coef, int coef_layout,
                                 int64_t coef_channel_stride, float* res, double* partial, rti_stream_t stream) {
-  if (!A || !I || !coef || !res) return fail(RTI_ERR_BAD_ARG, "rti_fit_residual: null pointer");
-  if (N <= 0 || P <= 0 || C <= 0 || C > 65535) return fail(RTI_ERR_BAD_ARG, "rti_fit_residual: bad N/P/C");
-  if (N < k) return fail(RTI_ERR_BAD_ARG, "rti_fit_residual: N=%d < k=%d", N, k);
-  if (in_dtype != RTI_F32 && in_dtype != RTI_U8 && in_dtype != RTI_I32)
-    return fail(RTI_ERR_UNSUPPORTED, "rti_fit_residual: input dtype %d", in_dtype);
-  if (coef_layout != RTI_COEF_PIXEL_MAJOR && coef_layout != RTI_COEF_PLANAR)
-    return fail(RTI_ERR_BAD_ARG, "rti_fit_residual: coef layout %d", coef_layout);
-  ResArgs a;
-  a.A = A;
-  a.k = k;
-  a.N = N;
-  a.I = I;
-  a.P = P;
-  a.lstride = light_stride ? light_stride : P;
-  a.cstride = channel_stride ? channel_stride : (int64_t)N * a.lstride;
-  a.coef = coef;
-  a.layout = coef_layout;
-  a.ocstride = coef_channel_stride ? coef_channel_stride : P * k;
-  a.res = res;
-  a.partial = partial;
-  a.C = C;
-  a.s = (hipStream_t)stream;
-  if (a.lstride < P) return fail(RTI_ERR_BAD_ARG, "rti_fit_residual: light_stride < P");
-  if (C > 1 && a.cstride < (int64_t)N * a.lstride) return fail(RTI_ERR_BAD_ARG, "rti_fit_residual: channel_stride");
-  if (C > 1 && a.ocstride < P * k) return fail(RTI_ERR_BAD_ARG, "rti_fit_residual: coef_channel_stride");
-  const size_t es = in_dtype == RTI_U8 ? 1 : 4;
-  const bool vec4 = P % 4 == 0 && a.lstride % 4 == 0 && a.cstride % 4 == 0 && aligned_to(I, 4 * es) &&
-                    aligned_to(res, 16) && aligned_to(coef, 16) && a.ocstride % 4 == 0;
-  switch (in_dtype) {
-    case RTI_F32: return launch_res_k<float>(a, vec4);
-    case RTI_U8: return launch_res_k<uint8_t>(a, vec4);
-    default: return launch_res_k<int32_t>(a, vec4);
-  }
+  const char* const E = "rti_fit_residual";
+  if (int st = check_pointers(E, {A, I, coef, res})) return st;
+  if (int st = check_extents(E, "N/P/C", N, P, C)) return st;
+  if (int st = check_lights(E, N, k)) return st;
+  if (int st = check_in_dtype(E, in_dtype)) return st;
+  if (int st = check_coef_layout(E, coef_layout)) return st;
+  const ResArgs a{A, stack_view(I, in_dtype, N, P, C, light_stride, channel_stride),
+                  coef_view(coef, coef_layout, k, P, coef_channel_stride), res, partial,
+                  (hipStream_t)stream};
+  if (int st = check_stack_strides(E, a.in)) return st;
+  if (int st = check_coef_stride(E, a.coef, P, C)) return st;
+  const bool vec4 = stack_vec_ok_any_c(a.in, 4) && aligned_to(res, 16) && coef_vec_ok_any_c(a.coef);
+  return with_in_dtype(in_dtype, [&](auto t) { return launch_res_k<decltype(t)>(a, vec4); });
 }

@@ -407,3 +407,32 @@ def test_torch_ops(cuda, planar):
         torch.ops.rti.fit_accumulate(Ad.float(), It, st, True)
     with pytest.raises(ValueError):
         torch.ops.rti.fit_accum_solve(M, st[:6], 24, False, planar)
+
+
+# ---- 11. the same fit as the one-pass kernel, to the bit ------------------------------------------------------
+@pytest.mark.parametrize("dtype", [torch.float32, torch.uint8])
+@pytest.mark.parametrize("C", [1, 2])
+@pytest.mark.parametrize("P", [3080, P0])
+@pytest.mark.parametrize("basis,N", [("ptm", 9), ("hsh9", 12), ("hsh16", 19)])
+def test_same_bits_as_one_pass_fit(cuda, basis, N, P, C, dtype):
+    """rti.FitAccumulator(directions=) fed the whole stack in one add, then solve, against rti.fit_with_residual:
+    both run the same fma chains over U's rows in light order and the same steps from those sums to coefficients
+    and residuals (the tail of fitres_body, restated in fit_accum_solve_k), so every value has the same bits.  P = 3080 is a multiple of 4
+    but not of 256 (one launch holds whole staged waves, a partial wave and the unstaged rows), P = 549 takes one
+    pixel per lane.  int32 stacks are left out: the one-pass kernel widens them through float, accumulate converts
+    them to double directly, and above 2^24 the two legitimately differ."""
+    lu, lv, A, I = noisy(N, P, basis, integer=dtype == torch.uint8)
+    if dtype == torch.uint8:
+        I = np.clip(I, 0, 255)
+    if C == 1:
+        It, shape, kw = torch.as_tensor(I, device=cuda).to(dtype), (P,), {}
+    else:  # the stack and its pixel-reversed copy as [C, N, 1, P]
+        It = torch.as_tensor(np.stack([I, I[:, ::-1]])[:, :, None, :].copy(), device=cuda).to(dtype)
+        shape, kw = (1, P), dict(channels=2)
+    acc = rti.FitAccumulator(shape, basis, device=cuda, directions=(lu, lv), **kw).add(It)
+    for layout in ("pixel", "planar"):
+        coef, res = acc.solve(layout=layout)
+        c0, r0, _ = rti.fit_with_residual(It, lu, lv, basis, layout=layout)
+        assert coef.shape == c0.shape and res.shape == r0.shape
+        assert torch.equal(coef, c0), (layout, int((coef != c0).sum()))
+        assert torch.equal(res, r0), (layout, int((res != r0).sum()))
