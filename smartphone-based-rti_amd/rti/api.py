@@ -53,6 +53,19 @@ def _f32_host(x, name):
     return a
 
 
+def _dirs(lu, lv):
+    """One light set's directions as two fp32 host arrays of equal length."""
+    lu, lv = _f32_host(lu, "lu"), _f32_host(lv, "lv")
+    if lu.size != lv.size:
+        raise ValueError("lu and lv differ in length")
+    return lu, lv
+
+
+def _rcond(rcond):
+    """The C ABI's SVD threshold: negative = none (the reference's semantics)."""
+    return -1.0 if rcond is None else float(rcond)
+
+
 def _fptr(a):
     return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
 
@@ -63,9 +76,7 @@ def _dptr(a):
 
 def design_matrix(lu, lv, basis="ptm"):
     """Host fp64 design matrix [N, k] (analysis.py:280-291 for PTM)."""
-    lu, lv = _f32_host(lu, "lu"), _f32_host(lv, "lv")
-    if lu.size != lv.size:
-        raise ValueError("lu and lv differ in length")
+    lu, lv = _dirs(lu, lv)
     b = basis_id(basis)
     A = np.empty((lu.size, basis_terms(b)), dtype=np.float64)
     L.check(L.lib().rti_design_matrix(b, _fptr(lu), _fptr(lv), lu.size, _dptr(A)), "rti_design_matrix")
@@ -76,27 +87,22 @@ def pinv(lu, lv, basis="ptm", rcond=None):
     """Host fp64 pseudo-inverse [k, N] of the shared design (analysis.py:293-298).
 
     ``rcond=None`` keeps the reference's semantics (no threshold)."""
-    lu, lv = _f32_host(lu, "lu"), _f32_host(lv, "lv")
-    if lu.size != lv.size:
-        raise ValueError("lu and lv differ in length")
+    lu, lv = _dirs(lu, lv)
     b = basis_id(basis)
     out = np.empty((basis_terms(b), lu.size), dtype=np.float64)
-    rc = -1.0 if rcond is None else float(rcond)
-    L.check(L.lib().rti_pinv(b, _fptr(lu), _fptr(lv), lu.size, rc, _dptr(out)), "rti_pinv")
+    L.check(L.lib().rti_pinv(b, _fptr(lu), _fptr(lv), lu.size, _rcond(rcond), _dptr(out)), "rti_pinv")
     return out
 
 
 def gram_inverse(lu, lv, basis="ptm", rcond=None):
     """Host fp64 Gram (pseudo-)inverse (AᵀA)⁺ [k, k] of the shared design (pinv = ginv·Aᵀ; the
     same SVD and rcond semantics as ``pinv``)."""
-    lu, lv = _f32_host(lu, "lu"), _f32_host(lv, "lv")
-    if lu.size != lv.size:
-        raise ValueError("lu and lv differ in length")
+    lu, lv = _dirs(lu, lv)
     b = basis_id(basis)
     k = basis_terms(b)
     out = np.empty((k, k), dtype=np.float64)
-    rc = -1.0 if rcond is None else float(rcond)
-    L.check(L.lib().rti_gram_inverse(b, _fptr(lu), _fptr(lv), lu.size, rc, _dptr(out)), "rti_gram_inverse")
+    L.check(L.lib().rti_gram_inverse(b, _fptr(lu), _fptr(lv), lu.size, _rcond(rcond), _dptr(out)),
+            "rti_gram_inverse")
     return out
 
 
@@ -104,42 +110,50 @@ def lsq_factors(lu, lv, basis="ptm", rcond=None):
     """Host fp64 thin-SVD factors ``(U [N, k], W [k, k])`` of the shared design, split as the
     reference's solve is (analysis.py:295-298: ``c = uᵀL; w = c/s; a = vᵀw``): U = the orthonormal
     left singular vectors, W = V Σ⁻¹, so pinv = W·Uᵀ (rcond as ``pinv``)."""
-    lu, lv = _f32_host(lu, "lu"), _f32_host(lv, "lv")
-    if lu.size != lv.size:
-        raise ValueError("lu and lv differ in length")
+    lu, lv = _dirs(lu, lv)
     b = basis_id(basis)
     k = basis_terms(b)
     U = np.empty((lu.size, k), dtype=np.float64)
     W = np.empty((k, k), dtype=np.float64)
-    rc = -1.0 if rcond is None else float(rcond)
-    L.check(L.lib().rti_lsq_factors(b, _fptr(lu), _fptr(lv), lu.size, rc, _dptr(U), _dptr(W)), "rti_lsq_factors")
+    L.check(L.lib().rti_lsq_factors(b, _fptr(lu), _fptr(lv), lu.size, _rcond(rcond), _dptr(U), _dptr(W)),
+            "rti_lsq_factors")
     return U, W
+
+
+# the 8-bit matrix-core forms of the shared fit: form -> librti's (operator_bytes, operator builder, fit entry,
+# max_lights), looked up when used (importing this module does not load the library)
+_U8_FORMS = {
+    "h16": ("rti_h16_operator_bytes", "rti_h16_operator", "rti_fit_shared_h16", "rti_fit_shared_h16_max_lights"),
+    "q8": ("rti_q8_operator_bytes", "rti_q8_operator", "rti_fit_shared_q8", "rti_fit_shared_q8_max_lights"),
+}
+
+
+def _u8_form(form):
+    return tuple(getattr(L.lib(), name) for name in _U8_FORMS[form])
+
+
+def _u8_operator(form, pinv64):
+    pv = np.ascontiguousarray(np.asarray(pinv64, np.float64))
+    k, N = pv.shape
+    nbytes, build = _u8_form(form)[:2]
+    nb = int(nbytes(k, N))
+    if nb <= 0:
+        raise ValueError(f"no {form} operator for k={k}, N={N}")
+    op = np.zeros(nb, dtype=np.uint8)
+    L.check(build(_dptr(pv), k, N, ctypes.c_void_p(op.ctypes.data)), _U8_FORMS[form][1])
+    return op
 
 
 def q8_operator(pinv64):
     """Host: the fixed-point int8-digit form of an fp64 operator [k, N] for ``rti_fit_shared_q8`` (8-bit
     stacks on the int8 matrix cores; layout in csrc/rti_q8.h).  Raises ValueError for non-finite entries."""
-    pv = np.ascontiguousarray(np.asarray(pinv64, np.float64))
-    k, N = pv.shape
-    nb = int(L.lib().rti_q8_operator_bytes(k, N))
-    if nb <= 0:
-        raise ValueError(f"no q8 operator for k={k}, N={N}")
-    op = np.zeros(nb, dtype=np.uint8)
-    L.check(L.lib().rti_q8_operator(_dptr(pv), k, N, ctypes.c_void_p(op.ctypes.data)), "rti_q8_operator")
-    return op
+    return _u8_operator("q8", pinv64)
 
 
 def h16_operator(pinv64):
     """Host: the split-fp16 form of an fp64 operator [k, N] for ``rti_fit_shared_h16`` (8-bit stacks on the
     fp16 matrix cores; layout in csrc/rti_fit_h16.hip).  Raises ValueError for non-finite entries."""
-    pv = np.ascontiguousarray(np.asarray(pinv64, np.float64))
-    k, N = pv.shape
-    nb = int(L.lib().rti_h16_operator_bytes(k, N))
-    if nb <= 0:
-        raise ValueError(f"no h16 operator for k={k}, N={N}")
-    op = np.zeros(nb, dtype=np.uint8)
-    L.check(L.lib().rti_h16_operator(_dptr(pv), k, N, ctypes.c_void_p(op.ctypes.data)), "rti_h16_operator")
-    return op
+    return _u8_operator("h16", pinv64)
 
 
 def _check_operator(op_dev, nbytes, form, k, N):
@@ -151,25 +165,30 @@ def _check_operator(op_dev, nbytes, form, k, N):
                          f"bytes for k={k}, N={N}: build it with rti.{form}_operator(pinv) for this light set")
 
 
+def _fit_u8_into(form, op_dev, I, coef, k, layout, flags):
+    C, N, P = (1, *I.shape) if I.dim() == 2 else I.shape
+    nbytes, _, entry, _ = _u8_form(form)
+    _check_operator(op_dev, int(nbytes(k, N)), form, k, N)
+    st = entry(_vp(op_dev), k, N, _vp(I), P, C, P, N * P, _vp(coef), _layout_id(layout), P * k, int(flags),
+               _stream_of(I))
+    L.check(st, _U8_FORMS[form][2])
+    return coef
+
+
 def fit_h16_into(op_dev, I, coef, *, k, layout="pixel", flags=0):
     """Launch ``rti_fit_shared_h16`` on preallocated tensors: op_dev = h16_operator(...) on the device
     (uint8), I a contiguous uint8 CUDA [N, P] or [C, N, P] stack, coef fp32 as fit_shared_into."""
-    if I.dim() == 2:
-        C, (N, P) = 1, I.shape
-    else:
-        C, N, P = I.shape
-    _check_operator(op_dev, int(L.lib().rti_h16_operator_bytes(k, N)), "h16", k, N)
-    st = L.lib().rti_fit_shared_h16(_vp(op_dev), k, N, _vp(I), P, C, P, N * P, _vp(coef), _layout_id(layout),
-                                    P * k, int(flags), _stream_of(I))
-    L.check(st, "rti_fit_shared_h16")
-    return coef
+    return _fit_u8_into("h16", op_dev, I, coef, k, layout, flags)
+
+
+def _u8_max_lights(form):
+    return int(_u8_form(form)[3]())
 
 
 def q8_supported(I, k, N, P, kernel="q8"):
     """Whether ``rti_fit_shared_q8`` (kernel="q8") or ``rti_fit_shared_h16`` (kernel="h16") takes this contiguous
     stack of P-pixel planes (uint8, k in {6, 9, 16}, N within the kernel's LDS budget, 16-byte aligned planes)."""
-    fn = L.lib().rti_fit_shared_h16_max_lights if kernel == "h16" else L.lib().rti_fit_shared_q8_max_lights
-    if I.dtype != torch.uint8 or k not in (6, 9, 16) or N > int(fn()):
+    if I.dtype != torch.uint8 or k not in (6, 9, 16) or N > _u8_max_lights("h16" if kernel == "h16" else "q8"):
         return False
     return P % 16 == 0 and I.data_ptr() % 16 == 0
 
@@ -177,15 +196,7 @@ def q8_supported(I, k, N, P, kernel="q8"):
 def fit_q8_into(op_dev, I, coef, *, k, layout="pixel", flags=0):
     """Launch ``rti_fit_shared_q8`` on preallocated tensors: op_dev = q8_operator(...) on the device (uint8),
     I a contiguous uint8 CUDA [N, P] or [C, N, P] stack, coef fp32 as fit_shared_into."""
-    if I.dim() == 2:
-        C, (N, P) = 1, I.shape
-    else:
-        C, N, P = I.shape
-    _check_operator(op_dev, int(L.lib().rti_q8_operator_bytes(k, N)), "q8", k, N)
-    st = L.lib().rti_fit_shared_q8(_vp(op_dev), k, N, _vp(I), P, C, P, N * P, _vp(coef), _layout_id(layout), P * k,
-                                   int(flags), _stream_of(I))
-    L.check(st, "rti_fit_shared_q8")
-    return coef
+    return _fit_u8_into("q8", op_dev, I, coef, k, layout, flags)
 
 
 _PM_KERNELS = ("auto", "valu", "mfma", "tile")  # the selectors rti_fit_shared_pm honours
@@ -211,12 +222,10 @@ def _fit_shared_pixel_major(I, lu, lv, b, k, rcond, cl, kernel, given_pixel_majo
         if v.dim() == 3 and C == 1:
             v = v.reshape(-1, N)
         v = v.reshape(C, -1, N)
-        lead4 = I.dim() == 4
     else:
         v = _pixel_major_of(I)
         C, N = v.shape[0], v.shape[2]
         spatial = tuple(I.shape[-2:]) if I.dim() >= 3 else (I.shape[-1],)
-        lead4 = I.dim() == 4
     P = v.shape[1]
     if N < k:
         raise ValueError(f"shapes not aligned: {N} lights < {k} basis terms (analysis.py:298)")
@@ -225,12 +234,10 @@ def _fit_shared_pixel_major(I, lu, lv, b, k, rcond, cl, kernel, given_pixel_majo
         raise ValueError(f"{pv.shape[1]} light directions for {N} intensity values per pixel")
     if I.dtype not in _IN_DTYPES:
         raise ValueError(f"I dtype {I.dtype} unsupported (float32, uint8 or int32)")
-    coef = torch.empty((C, P, k) if cl == L.RTI_COEF_PIXEL_MAJOR else (C, k, P), dtype=torch.float32,
-                       device=I.device)
+    coef = _coef_empty(C, P, k, cl, torch.float32, I.device)
     fit_shared_pm_into(torch.as_tensor(pv.astype(np.float32), device=I.device), v, coef, k=k, layout=cl,
                        kernel=kernel)
-    out = coef.reshape((C,) + spatial + (k,)) if cl == L.RTI_COEF_PIXEL_MAJOR else coef.reshape((C, k) + spatial)
-    return out if lead4 else out[0]
+    return _unflatten(coef, spatial, I.dim() == 4, cl)
 
 
 def basis_eval(lu, lv, basis="ptm"):
@@ -264,16 +271,58 @@ def _layout_id(layout):
     raise ValueError(f"unknown coefficient layout {layout!r} (expected 'pixel' or 'planar')")
 
 
+def _kernel_word(kernel):
+    """A kernel selector by name, or an integer kernel word as it is (the C entries refuse bits they do not
+    document)."""
+    return _KERNELS[kernel] if isinstance(kernel, str) else int(kernel)
+
+
+def _stack_shape(I):
+    """A light-major stack [N, P], [N, H, W] or [C, N, H, W] -> (C, N, P, spatial)."""
+    if I.dim() == 2:
+        (N, P), C, spatial = I.shape, 1, (I.shape[1],)
+    elif I.dim() == 3:
+        N, H, W = I.shape
+        C, P, spatial = 1, H * W, (H, W)
+    elif I.dim() == 4:
+        C, N, H, W = I.shape
+        P, spatial = H * W, (H, W)
+    else:
+        raise ValueError("I must be [N, P], [N, H, W] or [C, N, H, W]")
+    return C, N, P, spatial
+
+
+def _stack3(I, C, N, P):
+    """The stack as the launchers take it: contiguous [C, N, P] (a copy only if I is not contiguous)."""
+    return I.contiguous().reshape(C, N, P)
+
+
+def _coef_empty(C, P, k, layout, dtype, device):
+    """The coefficient tensor a launcher fills: [C, P, k] (pixel-major) or [C, k, P] (planar)."""
+    shape = (C, P, k) if _layout_id(layout) == L.RTI_COEF_PIXEL_MAJOR else (C, k, P)
+    return torch.empty(shape, dtype=dtype, device=device)
+
+
+def _unflatten(t, spatial, lead, layout=None):
+    """A launcher's output back in the caller's shape: a per-pixel map [C, P] -> [C, *spatial] (a per-channel
+    scalar [C] with spatial = ()), or with ``layout`` coefficients [C, P, k] -> [C, *spatial, k] / [C, k, P] ->
+    [C, k, *spatial]; without ``lead`` (the input had no channel axis) the leading C is dropped."""
+    if layout is None:
+        out = t.reshape(t.shape[:1] + spatial)
+    elif _layout_id(layout) == L.RTI_COEF_PIXEL_MAJOR:
+        out = t.reshape(t.shape[:1] + spatial + t.shape[2:])
+    else:
+        out = t.reshape(t.shape[:2] + spatial)
+    return out if lead else out[0]
+
+
 def fit_shared_into(pinv_dev, I, coef, *, k, layout="pixel", kernel="auto", nontemporal=False, flags=0):
     """Launch ``rti_fit_shared`` on preallocated tensors (no allocation, graph-capturable).
 
     pinv_dev: CUDA fp32 [k, N]; I: CUDA [C, N, P] or [N, P] (contiguous
     light-major, fp32/u8/int32); coef: CUDA fp32 [C, P, k] / [C, k, P]."""
-    if I.dim() == 2:
-        C, (N, P) = 1, I.shape
-    else:
-        C, N, P = I.shape
-    kern = _KERNELS[kernel] if isinstance(kernel, str) else int(kernel)
+    C, N, P = (1, *I.shape) if I.dim() == 2 else I.shape
+    kern = _kernel_word(kernel)
     if nontemporal:
         kern |= L.RTI_KERNEL_NONTEMPORAL
     kern |= int(flags)
@@ -297,7 +346,7 @@ def fit_shared_pm_into(pinv_dev, I, coef, *, k, layout="pixel", kernel="auto", f
         I3 = I3.contiguous()
     ps = I3.stride(1) if P > 1 else N
     cs = I3.stride(0) if C > 1 else P * ps
-    kern = (_KERNELS[kernel] if isinstance(kernel, str) else int(kernel)) | int(flags)
+    kern = _kernel_word(kernel) | int(flags)
     st = L.lib().rti_fit_shared_pm(_vp(pinv_dev), k, N, _vp(I3), _IN_DTYPES[I.dtype], P, C, ps, cs, _vp(coef),
                                    _layout_id(layout), P * k, kern, _stream_of(I))
     L.check(st, "rti_fit_shared_pm")
@@ -369,48 +418,28 @@ def fit(I, lu=None, lv=None, basis="ptm", mode="shared", rcond=None, *, cams=Non
         if (stack == "auto" and not I.is_contiguous() and I.dtype in (torch.float32, torch.int32)
                 and kernel in _PM_KERNELS and not nontemporal and _pixel_major_of(I) is not None):
             return _fit_shared_pixel_major(I, lu, lv, b, k, rcond, cl, kernel, False)
-        lead = I.shape[:-2] if I.dim() >= 3 else I.shape[:-1]
-        if I.dim() == 2:
-            N, P = I.shape
-            C, spatial = 1, (P,)
-        elif I.dim() == 3:
-            N, H, W = I.shape
-            C, P, spatial = 1, H * W, (H, W)
-        elif I.dim() == 4:
-            C, N, H, W = I.shape
-            P, spatial = H * W, (H, W)
-        else:
-            raise ValueError("I must be [N, P], [N, H, W] or [C, N, H, W]")
-        del lead
+        C, N, P, spatial = _stack_shape(I)
         if N < k:
             raise ValueError(f"shapes not aligned: {N} lights < {k} basis terms (analysis.py:298)")
         pv = pinv(lu, lv, b, rcond)
         if pv.shape[1] != N:
             raise ValueError(f"{pv.shape[1]} light directions for {N} intensity planes")
-        Ic = I.contiguous().reshape(C, N, P)
-        shape = (C, P, k) if cl == L.RTI_COEF_PIXEL_MAJOR else (C, k, P)
-        coef = torch.empty(shape, dtype=torch.float32, device=I.device)
+        Ic = _stack3(I, C, N, P)
+        coef = _coef_empty(C, P, k, cl, torch.float32, I.device)
         # 8-bit stacks (the reference's V channel): AUTO runs the split-fp16 fit on the fp16 matrix cores
         # (kernel="h16"); kernel="q8" the int8 fixed-point form (exact sums); both need a finite
         # operator (a rank-deficient light set without rcond keeps the fp32 path and the reference's NaN)
         mk = "h16" if kernel == "auto" else kernel
         if mk in ("h16", "q8") and q8_supported(Ic, k, N, P, mk) and np.isfinite(pv).all():
-            if mk == "h16":
-                fit_h16_into(torch.as_tensor(h16_operator(pv), device=I.device), Ic, coef, k=k, layout=cl)
-            else:
-                fit_q8_into(torch.as_tensor(q8_operator(pv), device=I.device), Ic, coef, k=k, layout=cl)
+            _fit_u8_into(mk, torch.as_tensor(_u8_operator(mk, pv), device=I.device), Ic, coef, k, cl, 0)
         elif kernel in ("q8", "h16"):
-            fn = L.lib().rti_fit_shared_h16_max_lights if kernel == "h16" else L.lib().rti_fit_shared_q8_max_lights
-            raise NotImplementedError(f"kernel={kernel!r} needs a uint8 stack, k in (6, 9, 16), N <= {int(fn())}, "
-                                      "16-pixel-aligned planes and a finite pseudo-inverse")
+            raise NotImplementedError(f"kernel={kernel!r} needs a uint8 stack, k in (6, 9, 16), "
+                                      f"N <= {_u8_max_lights(kernel)}, 16-pixel-aligned planes and a finite "
+                                      "pseudo-inverse")
         else:
             pinv_dev = torch.as_tensor(pv.astype(np.float32), device=I.device)
             fit_shared_into(pinv_dev, Ic, coef, k=k, layout=cl, kernel=kernel, nontemporal=nontemporal)
-        if cl == L.RTI_COEF_PIXEL_MAJOR:
-            out = coef.reshape((C,) + spatial + (k,))
-        else:
-            out = coef.reshape((C, k) + spatial)
-        return out if I.dim() == 4 else out[0]
+        return _unflatten(coef, spatial, I.dim() == 4, cl)
     if mode != "perpixel":
         raise ValueError(f"unknown mode {mode!r} (expected 'shared' or 'perpixel')")
     if basis_id(basis) != L.RTI_BASIS_PTM6:
@@ -418,7 +447,7 @@ def fit(I, lu=None, lv=None, basis="ptm", mode="shared", rcond=None, *, cams=Non
     cdt = _COEF_DTYPES.get(coef_dtype)
     if cdt is None:
         raise ValueError("coef_dtype must be torch.float32 or torch.float64")
-    rc = -1.0 if rcond is None else float(rcond)
+    rc = _rcond(rcond)
     if cams is not None:
         if I.dim() != 3:
             raise ValueError("per-pixel camera mode needs I light-major [N, H, W]")
@@ -452,6 +481,19 @@ def fit(I, lu=None, lv=None, basis="ptm", mode="shared", rcond=None, *, cams=Non
     return coef
 
 
+def fit_residual_into(A_dev, I3, coef, res, partial, *, k, layout="pixel"):
+    """Launch ``rti_fit_residual`` on preallocated tensors (no allocation, graph-capturable).
+
+    A_dev fp32 [N, k] (``design_matrix`` rounded to fp32, on the device), I3 CUDA [C, N, P] light-major
+    (fp32/u8/int32), coef fp32 [C, P, k] / [C, k, P] contiguous, res fp32 [C, P], partial fp64
+    [C, rti_fit_residual_blocks(P)] zeroed (or None): each workgroup's residual energy."""
+    C, N, P = I3.shape
+    st = L.lib().rti_fit_residual(_vp(A_dev), k, N, _vp(I3), _IN_DTYPES[I3.dtype], P, C, P, N * P, _vp(coef),
+                                  _layout_id(layout), P * k, _vp(res), None if partial is None else _vp(partial),
+                                  _stream_of(I3))
+    L.check(st, "rti_fit_residual")
+
+
 def fit_residual(I, coef, lu, lv, basis="ptm", *, layout="pixel"):
     """Per-pixel RMS residual of a shared-direction fit (``rti_fit_residual``).
 
@@ -465,47 +507,21 @@ def fit_residual(I, coef, lu, lv, basis="ptm", *, layout="pixel"):
     cl = _layout_id(layout)
     b = basis_id(basis)
     k = basis_terms(b)
-    if I.dim() == 2:
-        (N, P), C, spatial = I.shape, 1, (I.shape[1],)
-    elif I.dim() == 3:
-        N, H, W = I.shape
-        C, P, spatial = 1, H * W, (H, W)
-    elif I.dim() == 4:
-        C, N, H, W = I.shape
-        P, spatial = H * W, (H, W)
-    else:
-        raise ValueError("I must be [N, P], [N, H, W] or [C, N, H, W]")
+    C, N, P, spatial = _stack_shape(I)
     if coef.dtype != torch.float32 or coef.numel() != C * P * k:
         raise ValueError(f"coef must be fp32 with {C}x{P}x{k} elements (the output of fit)")
     A = design_matrix(lu, lv, b)
     if A.shape[0] != N:
         raise ValueError(f"{A.shape[0]} light directions for {N} intensity planes")
     A_dev = torch.as_tensor(A.astype(np.float32), device=I.device).contiguous()
-    Ic = I.contiguous().reshape(C, N, P)
+    Ic = _stack3(I, C, N, P)
     cc = coef.contiguous()
     res = torch.empty((C, P), dtype=torch.float32, device=I.device)
     nb = int(L.lib().rti_fit_residual_blocks(P))
     partial = torch.zeros((C, nb), dtype=torch.float64, device=I.device)
-    st = L.lib().rti_fit_residual(_vp(A_dev), k, N, _vp(Ic), _IN_DTYPES[Ic.dtype], P, C, P, N * P, _vp(cc), cl,
-                                  P * k, _vp(res), _vp(partial), _stream_of(I))
-    L.check(st, "rti_fit_residual")
+    fit_residual_into(A_dev, Ic, cc, res, partial, k=k, layout=cl)
     rms = torch.sqrt(partial.sum(dim=1) / (P * N))
-    res = res.reshape((C,) + spatial)
-    return (res, rms) if I.dim() == 4 else (res[0], rms[0])
-
-
-def _stack_shape(I):
-    if I.dim() == 2:
-        (N, P), C, spatial = I.shape, 1, (I.shape[1],)
-    elif I.dim() == 3:
-        N, H, W = I.shape
-        C, P, spatial = 1, H * W, (H, W)
-    elif I.dim() == 4:
-        C, N, H, W = I.shape
-        P, spatial = H * W, (H, W)
-    else:
-        raise ValueError("I must be [N, P], [N, H, W] or [C, N, H, W]")
-    return C, N, P, spatial
+    return _unflatten(res, spatial, I.dim() == 4), _unflatten(rms, (), I.dim() == 4)
 
 
 def fit_shared_residual_into(U_dev, W_dev, I3, coef, res, partial, *, k, layout="pixel", chunks=0):
@@ -549,15 +565,14 @@ def fit_with_residual(I, lu, lv, basis="ptm", rcond=None, *, layout="pixel", chu
     dev = I.device
     U_dev = torch.as_tensor(U, device=dev).contiguous()
     W_dev = torch.as_tensor(W, device=dev).contiguous()
-    Ic = I.contiguous().reshape(C, N, P)
-    coef = torch.empty((C, P, k) if cl == L.RTI_COEF_PIXEL_MAJOR else (C, k, P), dtype=torch.float32, device=dev)
+    Ic = _stack3(I, C, N, P)
+    coef = _coef_empty(C, P, k, cl, torch.float32, dev)
     res = torch.empty((C, P), dtype=torch.float32, device=dev)
     partial = torch.zeros((C, int(L.lib().rti_fit_shared_residual_blocks(P))), dtype=torch.float64, device=dev)
     fit_shared_residual_into(U_dev, W_dev, Ic, coef, res, partial, k=k, layout=cl, chunks=chunks)
     rms = torch.sqrt(partial.sum(dim=1) / (P * N))
-    coef = coef.reshape((C,) + spatial + (k,)) if cl == L.RTI_COEF_PIXEL_MAJOR else coef.reshape((C, k) + spatial)
-    res = res.reshape((C,) + spatial)
-    return (coef, res, rms) if I.dim() == 4 else (coef[0], res[0], rms[0])
+    lead = I.dim() == 4
+    return _unflatten(coef, spatial, lead, cl), _unflatten(res, spatial, lead), _unflatten(rms, (), lead)
 
 
 def fit_robust_into(A_dev, I3, coef, res, kept, fallback, *, k, lo, hi, min_lights, iters=0, delta=0.0,
@@ -613,8 +628,8 @@ def fit_robust(I, lu, lv, basis="ptm", *, lo=None, hi=None, min_lights=None, ite
     lo, hi = _robust_window(I, lo, hi)
     dev = I.device
     A_dev = torch.as_tensor(A, device=dev).contiguous()
-    Ic = I.contiguous().reshape(C, N, P)
-    coef = torch.empty((C, P, k) if cl == L.RTI_COEF_PIXEL_MAJOR else (C, k, P), dtype=torch.float32, device=dev)
+    Ic = _stack3(I, C, N, P)
+    coef = _coef_empty(C, P, k, cl, torch.float32, dev)
     res = torch.empty((C, P), dtype=torch.float32, device=dev)
     kept = torch.empty((C, P), dtype=torch.int32, device=dev)
     fallback = torch.zeros(1, dtype=torch.int32, device=dev)
@@ -623,9 +638,8 @@ def fit_robust(I, lu, lv, basis="ptm", *, lo=None, hi=None, min_lights=None, ite
                     delta=0.0 if delta is None else delta, layout=cl, kernel=kernel)
     if isinstance(stats, dict):
         stats["fallback_px"] = int(fallback.item())
-    coef = coef.reshape((C,) + spatial + (k,)) if cl == L.RTI_COEF_PIXEL_MAJOR else coef.reshape((C, k) + spatial)
-    res, kept = res.reshape((C,) + spatial), kept.reshape((C,) + spatial)
-    return (coef, res, kept) if I.dim() == 4 else (coef[0], res[0], kept[0])
+    lead = I.dim() == 4
+    return _unflatten(coef, spatial, lead, cl), _unflatten(res, spatial, lead), _unflatten(kept, spatial, lead)
 
 
 def fit_accumulate_into(R_dev, I3, state, *, k, init=False, light_stride=None):
@@ -782,13 +796,11 @@ class FitAccumulator:
             ginv = gram_inverse(np.asarray(self.lu, np.float32), np.asarray(self.lv, np.float32), self.basis, rcond)
             M_dev, orth = torch.as_tensor(ginv, device=dev).contiguous(), False
         C = self.state.shape[0]
-        coef = torch.empty((C, P, k) if cl == L.RTI_COEF_PIXEL_MAJOR else (C, k, P), dtype=torch.float32, device=dev)
+        coef = _coef_empty(C, P, k, cl, torch.float32, dev)
         res = torch.empty((C, P), dtype=torch.float32, device=dev)
         fit_accum_solve_into(M_dev, self.state, coef, res, k=k, n_lights=N, orth=orth, layout=cl)
-        sp = self.spatial
-        coef = coef.reshape((C,) + sp + (k,)) if cl == L.RTI_COEF_PIXEL_MAJOR else coef.reshape((C, k) + sp)
-        res = res.reshape((C,) + sp)
-        return (coef, res) if self.channels is not None else (coef[0], res[0])
+        lead = self.channels is not None
+        return _unflatten(coef, self.spatial, lead, cl), _unflatten(res, self.spatial, lead)
 
 
 def fit_chunked(chunks, shape, basis="ptm", *, rcond=None, layout="pixel", **kw):
@@ -922,9 +934,7 @@ def rbf_operator(lu, lv, qu, qv):
     """Host fp64 linear-RBF operator opT[N, E] (SciPy Rbf 'linear', analysis.py:249-260).
 
     Raises numpy.linalg.LinAlgError for a singular system, as SciPy does."""
-    lu, lv = _f32_host(lu, "lu"), _f32_host(lv, "lv")
-    if lu.size != lv.size:
-        raise ValueError("lu and lv differ in length")
+    lu, lv = _dirs(lu, lv)
     qu, qv = _query(qu, qv)
     out = np.empty((lu.size, qu.size), np.float64)
     L.check(L.lib().rti_rbf_operator(_fptr(lu), _fptr(lv), lu.size, _dptr(qu), _dptr(qv), qu.size, _dptr(out)),
@@ -934,12 +944,10 @@ def rbf_operator(lu, lv, qu, qv):
 
 def basis_operator(lu, lv, qu, qv, basis="ptm", rcond=None):
     """Host fp64 operator opT[N, E] = (B(q) · pinv)ᵀ: fit and evaluation fused (analysis.py:293-315)."""
-    lu, lv = _f32_host(lu, "lu"), _f32_host(lv, "lv")
-    if lu.size != lv.size:
-        raise ValueError("lu and lv differ in length")
+    lu, lv = _dirs(lu, lv)
     qu, qv = _query(qu, qv)
     out = np.empty((lu.size, qu.size), np.float64)
-    rc = -1.0 if rcond is None else float(rcond)
+    rc = _rcond(rcond)
     L.check(L.lib().rti_basis_operator(basis_id(basis), _fptr(lu), _fptr(lv), lu.size, _dptr(qu), _dptr(qv),
                                        qu.size, rc, _dptr(out)), "rti_basis_operator")
     return out
@@ -977,18 +985,9 @@ def apply_operator(opT, I, out_dtype=torch.float32, precision="auto"):
     if precision not in ("auto", "split16", "fp32"):
         raise ValueError("precision must be 'auto', 'split16' or 'fp32'")
     N, E = tuple(opT.shape)
-    if I.dim() == 2:
-        C, spatial = 1, (I.shape[1],)
-    elif I.dim() == 3:
-        C, spatial = 1, tuple(I.shape[1:])
-    elif I.dim() == 4:
-        C, spatial = I.shape[0], tuple(I.shape[2:])
-    else:
-        raise ValueError("I must be [N, P], [N, H, W] or [C, N, H, W]")
-    n_img = I.shape[-3] if I.dim() >= 3 else I.shape[0]
+    C, n_img, P, spatial = _stack_shape(I)
     if n_img != N:
         raise ValueError(f"operator has {N} lights, I has {n_img}")
-    P = int(np.prod(spatial))
     Ic = I.contiguous()
     out = torch.empty((C, E) + spatial, dtype=out_dtype, device=I.device)
     if precision == "split16" or (precision == "auto" and N <= 256):

@@ -26,6 +26,29 @@ def _in_dtype(I):
         raise ValueError(f"I dtype {I.dtype} unsupported (float32, uint8 or int32)")
 
 
+def _batched(I):
+    """[N, P] or [C, N, P] -> the contiguous [C, N, P] the launchers take."""
+    return I.contiguous() if I.dim() == 3 else I.contiguous().unsqueeze(0)
+
+
+def _lead(t):
+    """The caller's channel axis: (C,) of a 3-D stack or state, () of a 2-D one."""
+    return (t.shape[0],) if t.dim() == 3 else ()
+
+
+def _outputs(like, lead, P, k, planar, maps=()):
+    """An op's outputs on ``like``'s device: fp32 coefficients lead + [P, k] (or [k, P] if planar), then one
+    per-pixel map lead + [P] for each dtype of ``maps``.  The real ops pass lead = (C,) and un-batch after the
+    launch, their fakes the caller's own lead, so both shapes come from this expression."""
+    coef = like.new_empty(lead + ((k, P) if planar else (P, k)), dtype=torch.float32)
+    return (coef,) + tuple(like.new_empty(lead + (P,), dtype=dt) for dt in maps)
+
+
+def _unbatched(t, *outs):
+    """The outputs as the caller's 2-D or 3-D ``t`` asked for them: without the leading C for 2-D."""
+    return outs if t.dim() == 3 else tuple(o[0] for o in outs)
+
+
 @torch.library.custom_op("rti::fit_shared", mutates_args=())
 def fit_shared(pinv: torch.Tensor, I: torch.Tensor, planar: bool = False, kernel: int = 0) -> torch.Tensor:
     """coef = pinv (fp32 [k, N]) applied to I (CUDA [N, P] or [C, N, P]) -> [C?, P, k] or [C?, k, P]."""
@@ -36,24 +59,18 @@ def fit_shared(pinv: torch.Tensor, I: torch.Tensor, planar: bool = False, kernel
     _same_device(pinv=pinv, I=I)
     _in_dtype(I)
     k = pinv.shape[0]
-    I3 = I.contiguous() if I.dim() == 3 else I.contiguous().unsqueeze(0)
+    I3 = _batched(I)
     C, N, P = I3.shape
     if pinv.shape[1] != N:
         raise ValueError(f"pinv is [{k}, {pinv.shape[1]}] but I has {N} lights")
-    shape = (C, k, P) if planar else (C, P, k)
-    coef = torch.empty(shape, dtype=torch.float32, device=I.device)
+    coef, = _outputs(I, (C,), P, k, planar)
     api.fit_shared_into(pinv.contiguous(), I3, coef, k=k, layout="planar" if planar else "pixel", kernel=kernel)
-    return coef if I.dim() == 3 else coef[0]
+    return _unbatched(I, coef)[0]
 
 
 @fit_shared.register_fake
 def _(pinv, I, planar=False, kernel=0):
-    k = pinv.shape[0]
-    P = I.shape[-1]
-    shape = (k, P) if planar else (P, k)
-    if I.dim() == 3:
-        shape = (I.shape[0],) + shape
-    return I.new_empty(shape, dtype=torch.float32)
+    return _outputs(I, _lead(I), I.shape[-1], pinv.shape[0], planar)[0]
 
 
 @torch.library.custom_op("rti::fit_shared_residual", mutates_args=())
@@ -74,32 +91,26 @@ def fit_shared_residual(U: torch.Tensor, W: torch.Tensor, I: torch.Tensor, plana
         raise ValueError("U and W must be float64 (rti.lsq_factors)")
     _same_device(U=U, W=W, I=I)
     _in_dtype(I)
-    I3 = I.contiguous() if I.dim() == 3 else I.contiguous().unsqueeze(0)
+    I3 = _batched(I)
     C, N, P = I3.shape
     k = U.shape[1]
     if U.shape[0] != N or W.shape != (k, k):
         raise ValueError(f"U must be [{N}, k] and W [k, k]; got {tuple(U.shape)} and {tuple(W.shape)}")
     if N < k:
         raise ValueError(f"shapes not aligned: {N} lights < {k} basis terms (analysis.py:298)")
-    coef = torch.empty((C, k, P) if planar else (C, P, k), dtype=torch.float32, device=I.device)
-    res = torch.empty((C, P), dtype=torch.float32, device=I.device)
+    coef, res = _outputs(I, (C,), P, k, planar, (torch.float32,))
     partial = torch.zeros((C, int(L.lib().rti_fit_shared_residual_blocks(P))), dtype=torch.float64, device=I.device)
     api.fit_shared_residual_into(U.contiguous(), W.contiguous(), I3, coef, res, partial, k=k,
                                  layout="planar" if planar else "pixel", chunks=chunks)
-    if I.dim() == 2:
-        return coef[0], res[0], partial[0]
-    return coef, res, partial
+    return _unbatched(I, coef, res, partial)
 
 
 @fit_shared_residual.register_fake
 def _(U, W, I, planar=False, chunks=0):
-    k = U.shape[1]
     P = I.shape[-1]
-    lead = (I.shape[0],) if I.dim() == 3 else ()
     nb = (P + 255) // 256  # rti_fit_shared_residual_blocks(P): one slot per 256-pixel workgroup span
-    return (I.new_empty(lead + ((k, P) if planar else (P, k)), dtype=torch.float32),
-            I.new_empty(lead + (P,), dtype=torch.float32),
-            I.new_empty(lead + (nb,), dtype=torch.float64))
+    return _outputs(I, _lead(I), P, U.shape[1], planar, (torch.float32,)) + (
+        I.new_empty(_lead(I) + (nb,), dtype=torch.float64),)
 
 
 @torch.library.custom_op("rti::fit_robust", mutates_args=())
@@ -116,31 +127,22 @@ def fit_robust(A: torch.Tensor, I: torch.Tensor, lo: float, hi: float, min_light
         raise ValueError("A must be float64 (rti.design_matrix)")
     _same_device(A=A, I=I)
     _in_dtype(I)
-    I3 = I.contiguous() if I.dim() == 3 else I.contiguous().unsqueeze(0)
+    I3 = _batched(I)
     C, N, P = I3.shape
     k = A.shape[1]
     if A.shape[0] != N:
         raise ValueError(f"A must be [{N}, k]; got {tuple(A.shape)}")
-    coef = torch.empty((C, k, P) if planar else (C, P, k), dtype=torch.float32, device=I.device)
-    res = torch.empty((C, P), dtype=torch.float32, device=I.device)
-    kept = torch.empty((C, P), dtype=torch.int32, device=I.device)
+    coef, res, kept = _outputs(I, (C,), P, k, planar, (torch.float32, torch.int32))
     fallback = torch.zeros(1, dtype=torch.int32, device=I.device)
     api.fit_robust_into(A.contiguous(), I3, coef, res, kept, fallback, k=k, lo=lo, hi=hi, min_lights=min_lights,
                         iters=iters, delta=delta, layout="planar" if planar else "pixel", kernel=kernel)
-    if I.dim() == 2:
-        return coef[0], res[0], kept[0], fallback
-    return coef, res, kept, fallback
+    return _unbatched(I, coef, res, kept) + (fallback,)
 
 
 @fit_robust.register_fake
 def _(A, I, lo, hi, min_lights, iters=0, delta=0.0, planar=False, kernel=0):
-    k = A.shape[1]
-    P = I.shape[-1]
-    lead = (I.shape[0],) if I.dim() == 3 else ()
-    return (I.new_empty(lead + ((k, P) if planar else (P, k)), dtype=torch.float32),
-            I.new_empty(lead + (P,), dtype=torch.float32),
-            I.new_empty(lead + (P,), dtype=torch.int32),
-            I.new_empty((1,), dtype=torch.int32))
+    return _outputs(I, _lead(I), I.shape[-1], A.shape[1], planar, (torch.float32, torch.int32)) + (
+        I.new_empty((1,), dtype=torch.int32),)
 
 
 def _accum_state(state, k):
@@ -165,7 +167,7 @@ def fit_accumulate(R: torch.Tensor, I: torch.Tensor, state: torch.Tensor, init: 
         raise ValueError(f"I {tuple(I.shape)} and state {tuple(state.shape)} must both be 2-D or both 3-D")
     k = R.shape[1]
     s3 = _accum_state(state, k)
-    I3 = I.contiguous() if I.dim() == 3 else I.contiguous().unsqueeze(0)
+    I3 = _batched(I)
     if I3.shape[0] != s3.shape[0] or I3.shape[2] != s3.shape[2]:
         raise ValueError(f"I {tuple(I.shape)} does not match state {tuple(state.shape)}")
     api.fit_accumulate_into(R.contiguous(), I3, s3, k=k, init=init)
@@ -188,20 +190,15 @@ def fit_accum_solve(M: torch.Tensor, state: torch.Tensor, n_lights: int, orth: b
     k = M.shape[0]
     s3 = _accum_state(state, k)
     C, _, P = s3.shape
-    coef = torch.empty((C, k, P) if planar else (C, P, k), dtype=torch.float32, device=state.device)
-    res = torch.empty((C, P), dtype=torch.float32, device=state.device)
+    coef, res = _outputs(state, (C,), P, k, planar, (torch.float32,))
     api.fit_accum_solve_into(M.contiguous(), s3, coef, res, k=k, n_lights=n_lights, orth=orth,
                              layout="planar" if planar else "pixel")
-    return (coef, res) if state.dim() == 3 else (coef[0], res[0])
+    return _unbatched(state, coef, res)
 
 
 @fit_accum_solve.register_fake
 def _(M, state, n_lights, orth=False, planar=False):
-    k = M.shape[0]
-    P = state.shape[-1]
-    lead = (state.shape[0],) if state.dim() == 3 else ()
-    return (state.new_empty(lead + ((k, P) if planar else (P, k)), dtype=torch.float32),
-            state.new_empty(lead + (P,), dtype=torch.float32))
+    return _outputs(state, _lead(state), state.shape[-1], M.shape[0], planar, (torch.float32,))
 
 
 @torch.library.custom_op("rti::fit_residual", mutates_args=())
@@ -223,10 +220,7 @@ def fit_residual(A: torch.Tensor, I: torch.Tensor, coef: torch.Tensor) -> torch.
         raise ValueError(f"A must be [{N}, k] and coef [{P}, k]")
     Ic, Ac, cc = I.contiguous(), A.contiguous(), coef.contiguous()
     res = torch.empty(P, dtype=torch.float32, device=I.device)
-    st = L.lib().rti_fit_residual(api._vp(Ac), k, N, api._vp(Ic), api._IN_DTYPES[Ic.dtype], P, 1, P, N * P,
-                                  api._vp(cc), L.RTI_COEF_PIXEL_MAJOR, P * k, api._vp(res), None,
-                                  api._stream_of(I))
-    L.check(st, "rti_fit_residual")
+    api.fit_residual_into(Ac, Ic.unsqueeze(0), cc, res, None, k=k, layout="pixel")
     return res
 
 

@@ -260,7 +260,7 @@ class RowTiledFitter:
             self.cams = torch.as_tensor(cams_np, device=dev).contiguous()
             if self.cams.shape != (self.N, 3):
                 raise ValueError(f"cams must be [{self.N}, 3]")
-            self.rc = -1.0 if rcond is None else float(rcond)
+            self.rc = api._rcond(rcond)
             self.dtype = coef_dtype
         else:
             if lu is None or lv is None:
@@ -285,21 +285,19 @@ class RowTiledFitter:
             if isinstance(kernel, str) and kernel not in api._KERNELS and kernel not in ("h16", "q8"):
                 raise ValueError(f"unknown kernel {kernel!r}")
             if mk in ("h16", "q8"):
-                maxn = (L.lib().rti_fit_shared_h16_max_lights if mk == "h16" else
-                        L.lib().rti_fit_shared_q8_max_lights)()
-                ok = (stack == "light" and self.I.dtype == torch.uint8 and self.W % 16 == 0 and self.k in (6, 9, 16)
-                      and self.N <= int(maxn) and np.isfinite(pv).all() and self.I.data_ptr() % 16 == 0)
+                # q8_supported's rule on a row chunk's planes: W % 16 (chunks are whole rows), not P % 16
+                ok = (stack == "light" and api.q8_supported(self.I, self.k, self.N, self.W, mk)
+                      and np.isfinite(pv).all())
                 if ok:
                     self.u8 = mk
-                    self.u8_op = torch.as_tensor(api.h16_operator(pv) if mk == "h16" else api.q8_operator(pv),
-                                                 device=dev)
+                    self.u8_op = torch.as_tensor(api._u8_operator(mk, pv), device=dev)
                 elif kernel in ("h16", "q8"):
                     raise NotImplementedError(f"kernel={kernel!r} needs a light-major uint8 stack, W % 16 == 0, "
-                                              f"k in (6, 9, 16), N <= {int(maxn)} and a finite pseudo-inverse")
+                                              f"k in (6, 9, 16), N <= {api._u8_max_lights(mk)} and a finite "
+                                              "pseudo-inverse")
             # every other selector (string or integer kernel word) goes to rti_fit_shared / rti_fit_shared_pm
             # unchanged: the C entries refuse bits they do not document
-            self.kern = 0 if mk in ("h16", "q8") else (api._KERNELS[kernel] if isinstance(kernel, str)
-                                                       else int(kernel))
+            self.kern = 0 if mk in ("h16", "q8") else api._kernel_word(kernel)
         self.dt = api._IN_DTYPES[self.I.dtype]
         self.coef = torch.empty((self.C, self.h, self.W, self.k), dtype=self.dtype, device=dev)
         lead = (self.C,) if self.C > 1 or self.I.dim() == 4 else ()

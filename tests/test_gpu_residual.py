@@ -128,6 +128,25 @@ def test_custom_op_matches_api(cuda):
     assert torch.equal(got, res.reshape(-1))
 
 
+@pytest.mark.parametrize("in_dtype", [torch.float32, torch.uint8])
+@pytest.mark.parametrize("P", [37, 256])
+def test_custom_op_equals_api_small(cuda, P, in_dtype):
+    """The op and rti.fit_residual hand rti_fit_residual the same arguments: equal to the bit, on a ragged
+    tail (P = 37) and on one full 256-pixel workgroup span."""
+    from rti import ops  # noqa: F401  registers torch.ops.rti.*
+    n, k = 8, 6
+    lu, lv = o.synth_dirs(n, 3)
+    g = torch.Generator(device=cuda).manual_seed(P)
+    I = torch.randint(0, 256, (n, P), generator=g, device=cuda).to(in_dtype)
+    coef = rti.fit(I, lu, lv)
+    assert coef.shape == (P, k)
+    A = torch.as_tensor(rti.design_matrix(lu, lv).astype(np.float32), device=cuda)
+    got = torch.ops.rti.fit_residual(A, I, coef)
+    want = rti.fit_residual(I, coef, lu, lv)[0]
+    assert got.shape == (P,) and got.abs().max().item() > 0
+    assert torch.equal(got, want)
+
+
 @pytest.mark.parametrize("layout", ["pixel", "planar"])
 @pytest.mark.parametrize("in_dtype", [torch.float32, torch.uint8])
 def test_wide_lane_path_ragged(cuda, layout, in_dtype):
