@@ -490,6 +490,64 @@ int rti_relight(const void* coef, int coef_dtype, int basis, int64_t P, int coef
 int rti_relight_frame(const void* src, int src_dtype, int basis, int coef_layout, int64_t P,
                       double lu, double lv, const uint8_t* hsv, uint8_t* bgr, rti_stream_t stream);
 
+/* ---- device: PTM surface normals and enhanced relighting (rti_normals.hip) -------------
+ * What a fitted PTM says about the surface, after Malzbender, Gelb and Wolters (2001); the reference
+ * stops at the relit value, so these semantics are build-defined.  PTM-6 only:
+ *   L(u, v) = a0·u² + a1·v² + a2·u·v + a3·u + a4·v + a5
+ * (HSH has no closed-form maximum: any other basis returns RTI_ERR_UNSUPPORTED).
+ * All per-pixel arithmetic is fp64 from the F32 / F64 coefficients, every product, sum, quotient and
+ * square root rounded (no contraction), products and sums taken left to right as written, and the
+ * result rounded once to the output type.  Per pixel:
+ *   D = 4·a0·a1 − a2²,  S = a0² + a1² + ½·a2²
+ *   a maximum exists when every coefficient is finite, D > 1e-6·S and a0 < 0; then
+ *     u0 = (a2·a4 − 2·a1·a3)/D,  v0 = (a2·a3 − 2·a0·a4)/D,  r² = u0² + v0²
+ *   kind 0  a maximum with r² <= 1:       n = (u0, v0, sqrt(1 − r²))
+ *   kind 1  a maximum outside the disc:   n = (u0, v0, 0)/sqrt(r²), scaled radially onto the edge
+ *   kind 2  no maximum:                   g = (a3, a4, max(a5, 0)), n = g/‖g‖, (0, 0, 1) when ‖g‖ = 0
+ *                                         (the Lambertian reading of the linear terms)
+ *   kind 4  a non-finite coefficient:     n and peak are NaN           (3 is not used)
+ *   peak = L(n_x, n_y) with the unrounded fp64 normal, the six terms summed left to right as
+ *   rti_relight's F64 path sums them: an albedo proxy.
+ * rti_ptm_normals: coef as rti_relight (coef_layout [p][6] or [6][p]); normals: device fp32,
+ * normal_layout [p][3] or [3][p]; kind: NULL or device uint8 [P]; peak: NULL or device fp32 [P].
+ * 4·6 (or 8·6) bytes in and 12 (+ 1 + 4) out per pixel. */
+#define RTI_NORMAL_PIXEL_MAJOR   0   /* normals[p][3] */
+#define RTI_NORMAL_PLANAR        1   /* normals[3][p] */
+int rti_ptm_normals(const void* coef, int coef_dtype, int basis, int coef_layout, int64_t P,
+                    float* normals, int normal_layout,
+                    uint8_t* kind /* NULL ok */, float* peak /* NULL ok */, rti_stream_t stream);
+
+/* rti_relight_enhanced: one image out[P] at the light direction (lu, lv), computed from the coefficients
+ * alone (the peak is recomputed per pixel, no normal map is read: the 4k + 4 = 28 bytes per pixel of a
+ * one-direction rti_relight).  Pixels of kind 4 give NaN in both modes.
+ *   RTI_ENHANCE_DIFFUSE_GAIN, gain g >= 0: for pixels with a maximum (kinds 0 and 1), about the
+ *   UNPROJECTED stationary point (u0, v0):
+ *     a0' = g·a0, a1' = g·a1, a2' = g·a2
+ *     a3' = (1−g)·(2·a0·u0 + a2·v0) + a3
+ *     a4' = (1−g)·(2·a1·v0 + a2·u0) + a4
+ *     a5' = (1−g)·(a0·u0² + a1·v0² + a2·u0·v0) + (a3−a3')·u0 + (a4−a4')·v0 + a5
+ *   out = L'(lu, lv): the curvature scaled by g, the location and the height of the peak kept.  Pixels
+ *   of kind 2 give the plain L(lu, lv).  kd, ks and spec_exp are not used.
+ *   RTI_ENHANCE_SPECULAR: lw = sqrt(max(0, 1 − lu² − lv²)), H = (lu, lv, lw + 1)/‖·‖ (formed once on the
+ *   host in fp64), out = kd·L(lu, lv) + ks·max(0, n·H)^spec_exp with n the normal above and spec_exp an
+ *   integer in [1, 255] raised by repeated squaring (r = 1, b = x; for each bit of spec_exp from the
+ *   lowest: r = r·b if it is set, then b = b·b while higher bits remain).  gain is not used.
+ * out_dtype: F32 value; I32 / U8 as rti_relight (C truncation, NaN / overflow -> INT32_MIN; U8 = that
+ * clipped to [0, 255]).
+ * Both entries: device pointers, stream-ordered, no allocation, no synchronisation.  Every argument
+ * check answers before any HIP call.  RTI_ERR_BAD_ARG: null coef / normals / out; P < 1; an unknown
+ * coefficient layout, normal layout or mode; non-finite lu, lv, gain, kd or ks; gain < 0; spec_exp
+ * outside [1, 255] in specular mode.  RTI_ERR_UNSUPPORTED: a basis other than PTM-6, a coefficient
+ * dtype other than F32 / F64, an output dtype other than F32 / I32 / U8.  The vector path (one lane =
+ * 4 pixels) needs P % 4 == 0, coef 16-byte aligned and every output aligned to a lane's 4 elements;
+ * anything else, and the last partial 256-pixel chunk, runs one pixel per lane with the same arithmetic
+ * and bits. */
+#define RTI_ENHANCE_DIFFUSE_GAIN 1
+#define RTI_ENHANCE_SPECULAR     2
+int rti_relight_enhanced(const void* coef, int coef_dtype, int basis, int coef_layout, int64_t P,
+                         int mode, double gain, double kd, double ks, int spec_exp,
+                         double lu, double lv, void* out, int out_dtype, rti_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

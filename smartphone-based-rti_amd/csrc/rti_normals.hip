@@ -1,0 +1,472 @@
+// rti_normals.hip -- what a fitted PTM says about the surface (gfx950): per-pixel normals and the
+// enhanced renderings built on them (Malzbender, Gelb, Wolters 2001: diffuse gain, specular enhancement).
+//
+// The reference stops at the relit value (analysis.py:300-315, interactive_relighting.py:25-38); these
+// semantics are build-defined and stated in include/rti.h and DESIGN.md §4.5.  PTM-6 only: the biquadratic
+//     L(u, v) = a0·u² + a1·v² + a2·u·v + a3·u + a4·v + a5
+// has a closed-form stationary point, HSH has none.
+//
+//     rti_ptm_normals        coefficients -> normal [3], kind, peak value
+//     rti_relight_enhanced   coefficients -> one image at (lu, lv): diffuse gain or specular enhancement
+//
+// Every per-pixel quantity is computed in fp64 from the fp32 / fp64 coefficients with FP contraction off and
+// rounded once to the output type: D = 4·a0·a1 − a2² cancels badly in fp32.  The branches (interior maximum,
+// maximum outside the disc, no maximum, non-finite) are selects: a wave sees every kind.  The one square root
+// and the three divisions of the normal are shared by the kinds (x/1 is exact), so a pixel costs five fp64
+// divisions and one square root whatever its kind.
+//
+// Both kernels are streams with rti_relight's lane map: a lane owns 4 consecutive pixels, a wave 256, a block
+// 1024.  Pixel-major coefficient rows come in as coalesced 1-KiB wave loads parked in the wave's LDS slab
+// (relight_eval_major's staging); planar maps as 16-byte loads per plane.  Pixel-major normals (12 B per
+// pixel) leave through the same slab so that each store instruction writes one contiguous KiB (the VM_STAGE
+// idea of rti_fit.hip).  rti_relight_enhanced reads no normal map: it recomputes the peak from the
+// coefficients and moves the 4k + 4 = 28 B per pixel of a one-direction rti_relight.
+//
+// A launch whose P is no multiple of 4 or whose pointers are not aligned for the vector accesses, and the
+// last partial wave of any launch, take one pixel per lane (a wave still covers its 256 pixels, 64 at a
+// time) through the same per-pixel functions, so the bits do not depend on the path.
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+#include <type_traits>
+
+#include "rti_convert.h"
+#include "rti_stack.h"
+
+namespace rti {
+namespace {
+
+constexpr int K = 6;  // PTM-6
+typedef double doublex2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// ---- per-pixel arithmetic (fp64, no contraction; tests/normals_ref.py restates it line by line) --------------
+
+// L(u, v), the six terms summed left to right as rti_relight's fp64 path does
+__device__ __forceinline__ double ptm_value(const double (&a)[K], double u, double v) {
+#pragma clang fp contract(off)
+  double acc = a[0] * (u * u);
+  acc = acc + a[1] * (v * v);
+  acc = acc + a[2] * (u * v);
+  acc = acc + a[3] * u;
+  acc = acc + a[4] * v;
+  return acc + a[5];
+}
+
+struct Peak {
+  double u0, v0, r2;  // the stationary point and its squared radius (meaningful with has_max)
+  bool finite;        // every coefficient is finite
+  bool has_max;       // finite, D > 1e-6·S and a0 < 0
+};
+
+__device__ __forceinline__ Peak ptm_peak(const double (&a)[K]) {
+#pragma clang fp contract(off)
+  Peak k;
+  k.finite = true;
+#pragma unroll
+  for (int i = 0; i < K; ++i) k.finite = k.finite && fabs(a[i]) <= DBL_MAX;  // false for NaN
+  const double a22 = a[2] * a[2];
+  const double D = 4.0 * a[0] * a[1] - a22;
+  const double S = a[0] * a[0] + a[1] * a[1] + 0.5 * a22;
+  k.has_max = k.finite && D > 1e-6 * S && a[0] < 0.0;
+  k.u0 = (a[2] * a[4] - 2.0 * a[1] * a[3]) / D;
+  k.v0 = (a[2] * a[3] - 2.0 * a[0] * a[4]) / D;
+  k.r2 = k.u0 * k.u0 + k.v0 * k.v0;
+  return k;
+}
+
+// the normal and the pixel's kind: 0 interior maximum, 1 maximum outside the unit disc (scaled radially onto
+// its edge), 2 no maximum (the Lambertian reading of the linear terms), 4 non-finite (NaN)
+__device__ __forceinline__ int ptm_normal(const double (&a)[K], const Peak& k, double (&n)[3]) {
+#pragma clang fp contract(off)
+  const bool inside = k.has_max && k.r2 <= 1.0;
+  const bool outside = k.has_max && !inside;
+  const double g2 = a[5] > 0.0 ? a[5] : 0.0;
+  const double gg = a[3] * a[3] + a[4] * a[4] + g2 * g2;
+  const double s = sqrt(inside ? 1.0 - k.r2 : outside ? k.r2 : gg);
+  const bool flat = !k.has_max && s == 0.0;  // ‖g‖ = 0 -> (0, 0, 1)
+  const double nx = k.has_max ? k.u0 : a[3];
+  const double ny = k.has_max ? k.v0 : a[4];
+  const double nz = inside ? s : outside ? 0.0 : g2;
+  const double den = (inside || flat) ? 1.0 : s;
+  n[0] = (flat ? 0.0 : nx) / den;
+  n[1] = (flat ? 0.0 : ny) / den;
+  n[2] = (flat ? 1.0 : nz) / den;
+  if (!k.finite) n[0] = n[1] = n[2] = NAN;
+  return !k.finite ? 4 : inside ? 0 : outside ? 1 : 2;
+}
+
+// diffuse gain g: the curvature scaled by g about the unprojected stationary point, whose location and height
+// stay; pixels without a maximum keep their coefficients
+__device__ __forceinline__ double diffuse_gain_value(const double (&a)[K], const Peak& k, double g, double lu, double lv) {
+#pragma clang fp contract(off)
+  const double h = 1.0 - g, u0 = k.u0, v0 = k.v0;
+  double b[K];
+  b[0] = g * a[0];
+  b[1] = g * a[1];
+  b[2] = g * a[2];
+  b[3] = h * (2.0 * a[0] * u0 + a[2] * v0) + a[3];
+  b[4] = h * (2.0 * a[1] * v0 + a[2] * u0) + a[4];
+  b[5] = h * (a[0] * (u0 * u0) + a[1] * (v0 * v0) + a[2] * u0 * v0) + (a[3] - b[3]) * u0 + (a[4] - b[4]) * v0 + a[5];
+#pragma unroll
+  for (int i = 0; i < K; ++i) b[i] = k.has_max ? b[i] : a[i];
+  return k.finite ? ptm_value(b, lu, lv) : (double)NAN;
+}
+
+// x^e, 1 <= e <= 255, by repeated squaring (e is wave-uniform); no pow
+__device__ __forceinline__ double powi(double x, int e) {
+#pragma clang fp contract(off)
+  double r = 1.0, b = x;
+  for (;;) {
+    if (e & 1) r = r * b;
+    e >>= 1;
+    if (!e) return r;
+    b = b * b;
+  }
+}
+
+struct Enhance {
+  double gain, kd, ks;
+  int e;
+  double lu, lv;
+  double hx, hy, hz;  // the half vector between the light and the viewer (0, 0, 1), unit length
+};
+
+template <int MODE>
+__device__ __forceinline__ double enhanced_value(const double (&a)[K], const Enhance& q) {
+#pragma clang fp contract(off)
+  const Peak k = ptm_peak(a);
+  if constexpr (MODE == RTI_ENHANCE_DIFFUSE_GAIN) {
+    return diffuse_gain_value(a, k, q.gain, q.lu, q.lv);
+  } else {
+    double n[3];
+    ptm_normal(a, k, n);
+    const double c = n[0] * q.hx + n[1] * q.hy + n[2] * q.hz;
+    const double v = q.kd * ptm_value(a, q.lu, q.lv) + q.ks * powi(c > 0.0 ? c : 0.0, q.e);
+    return k.finite ? v : (double)NAN;
+  }
+}
+
+// ---- coefficient loads ------------------------------------------------------------------------------------------
+
+// LDS per wave in 16-byte units: the coefficient staging slab and / or the pixel-major normals' 3 KiB
+template <typename TC, int CL, bool STAGE_OUT>
+constexpr int slab_v4() {
+  const int in = CL == RTI_COEF_PIXEL_MAJOR ? 64 * K * (int)sizeof(TC) / 4 : 0;
+  const int out = STAGE_OUT ? 64 * 3 : 0;
+  return in > out ? in : (out > 0 ? out : 1);
+}
+
+// Pixel-major coefficient rows through LDS: relight_eval_major's load_coef_staged (rti_relight.hip), restated.
+// It is a copy because bench.py hashes rti_relight.hip and rti_convert.h to decide whether
+// profiles/traffic.json is stale, so neither file can grow a shared header's include.  The wave reads its 256
+// pixels' rows as PIECES coalesced 1-KiB non-temporal loads (lane l, piece j: bytes 16·(64·j + l) of the
+// chunk), parks them in its slab and reads back its own 4 pixels' rows.
+template <typename TC>
+__device__ __forceinline__ void load_rows_staged(const TC* __restrict__ coef, int64_t wave_px, int lane,
+                                                 floatx4* __restrict__ slab, double (&a)[4][K]) {
+  constexpr int PIECES = K * (int)sizeof(TC) / 4;  // 16-B pieces per lane: 6 (fp32) or 12 (fp64)
+  const floatx4* g = reinterpret_cast<const floatx4*>(coef + wave_px * K);
+  floatx4 t[PIECES];
+#pragma unroll
+  for (int j = 0; j < PIECES; ++j) t[j] = __builtin_nontemporal_load(g + j * 64 + lane);
+#pragma unroll
+  for (int j = 0; j < PIECES; ++j) slab[j * 64 + lane] = t[j];
+  wave_lds_sync();
+  union {
+    floatx4 v[PIECES];
+    TC c[4][K];
+  } u;
+#pragma unroll
+  for (int j = 0; j < PIECES; ++j) u.v[j] = slab[lane * PIECES + j];
+#pragma unroll
+  for (int v = 0; v < 4; ++v)
+#pragma unroll
+    for (int i = 0; i < K; ++i) a[v][i] = (double)u.c[v][i];
+}
+
+// planar maps: a lane's 4 pixels of one plane are 16 (fp32) or 32 (fp64) contiguous bytes
+template <typename TC>
+__device__ __forceinline__ void load_planes(const TC* __restrict__ coef, int64_t P, int64_t p0, double (&a)[4][K]) {
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    const TC* src = coef + (int64_t)i * P + p0;
+    if constexpr (std::is_same<TC, float>::value) {
+      const floatx4 t = __builtin_nontemporal_load(reinterpret_cast<const floatx4*>(src));
+#pragma unroll
+      for (int v = 0; v < 4; ++v) a[v][i] = (double)t[v];
+    } else {
+      const doublex2 lo = __builtin_nontemporal_load(reinterpret_cast<const doublex2*>(src));
+      const doublex2 hi = __builtin_nontemporal_load(reinterpret_cast<const doublex2*>(src) + 1);
+      a[0][i] = lo[0];
+      a[1][i] = lo[1];
+      a[2][i] = hi[0];
+      a[3][i] = hi[1];
+    }
+  }
+}
+
+template <typename TC, int CL>
+__device__ __forceinline__ void load_wave(const TC* __restrict__ coef, int64_t P, int64_t wave_px, int lane,
+                                          floatx4* __restrict__ slab, double (&a)[4][K]) {
+  if constexpr (CL == RTI_COEF_PIXEL_MAJOR)
+    load_rows_staged<TC>(coef, wave_px, lane, slab, a);
+  else
+    load_planes<TC>(coef, P, wave_px + 4 * lane, a);
+}
+
+template <typename TC, int CL>
+__device__ __forceinline__ void load_pixel(const TC* __restrict__ coef, int64_t P, int64_t p, double (&a)[K]) {
+#pragma unroll
+  for (int i = 0; i < K; ++i) a[i] = (double)(CL == RTI_COEF_PLANAR ? coef[(int64_t)i * P + p] : coef[p * K + i]);
+}
+
+// ---- kernels --------------------------------------------------------------------------------------------------
+// Both: a wave owns pixels [wave_px, wave_px + 256).  vec != 0 (P % 4 == 0, every pointer aligned for its vector
+// access) and the whole chunk inside the image: lane l owns pixels wave_px + 4l .. + 3.  Otherwise lane l takes
+// pixels wave_px + 64j + l, j = 0..3, one at a time.
+
+struct NormalOut {
+  float n[3];
+  float peak;
+  uint8_t kind;
+};
+
+__device__ __forceinline__ NormalOut normal_of(const double (&a)[K], bool want_peak) {
+  double n[3];
+  const int kind = ptm_normal(a, ptm_peak(a), n);
+  NormalOut o;
+  o.n[0] = (float)n[0];
+  o.n[1] = (float)n[1];
+  o.n[2] = (float)n[2];
+  o.kind = (uint8_t)kind;
+  o.peak = want_peak ? (float)(kind == 4 ? (double)NAN : ptm_value(a, n[0], n[1])) : 0.f;
+  return o;
+}
+
+template <typename TC, int CL, int NL>
+__global__ void __launch_bounds__(256)
+ptm_normals_k(const TC* __restrict__ coef, int64_t P, int vec, float* __restrict__ normals, uint8_t* __restrict__ kind,
+              float* __restrict__ peak) {
+  constexpr bool STAGE_OUT = NL == RTI_NORMAL_PIXEL_MAJOR;
+  constexpr int SLAB = slab_v4<TC, CL, STAGE_OUT>();
+  __shared__ floatx4 slabs[4 * SLAB];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
+  if (wave_px >= P) return;
+  floatx4* slab = slabs + wave * SLAB;
+  if (vec && wave_px + 256 <= P) {  // wave-uniform
+    const int64_t p0 = wave_px + 4 * lane;
+    double a[4][K];
+    load_wave<TC, CL>(coef, P, wave_px, lane, slab, a);
+    NormalOut o[4];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) o[v] = normal_of(a[v], peak != nullptr);
+    if (kind)
+      *reinterpret_cast<uint32_t*>(kind + p0) = (uint32_t)o[0].kind | ((uint32_t)o[1].kind << 8) |
+                                                ((uint32_t)o[2].kind << 16) | ((uint32_t)o[3].kind << 24);
+    if (peak) *reinterpret_cast<floatx4*>(peak + p0) = floatx4{o[0].peak, o[1].peak, o[2].peak, o[3].peak};
+    if constexpr (STAGE_OUT) {
+      // a lane's 48 B would be three stores strided 48 B across the wave: the wave's 3 KiB go through its slab
+      // (every lane has read its coefficient rows back by now) and leave as three contiguous 1-KiB stores
+      wave_lds_sync();
+      slab[lane * 3 + 0] = floatx4{o[0].n[0], o[0].n[1], o[0].n[2], o[1].n[0]};
+      slab[lane * 3 + 1] = floatx4{o[1].n[1], o[1].n[2], o[2].n[0], o[2].n[1]};
+      slab[lane * 3 + 2] = floatx4{o[2].n[2], o[3].n[0], o[3].n[1], o[3].n[2]};
+      wave_lds_sync();
+      floatx4* g = reinterpret_cast<floatx4*>(normals + wave_px * 3);
+#pragma unroll
+      for (int j = 0; j < 3; ++j) g[j * 64 + lane] = slab[j * 64 + lane];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        *reinterpret_cast<floatx4*>(normals + (int64_t)i * P + p0) = floatx4{o[0].n[i], o[1].n[i], o[2].n[i], o[3].n[i]};
+    }
+    return;
+  }
+  for (int j = 0; j < 4; ++j) {
+    const int64_t p = wave_px + 64 * j + lane;
+    if (p >= P) break;
+    double a[K];
+    load_pixel<TC, CL>(coef, P, p, a);
+    const NormalOut o = normal_of(a, peak != nullptr);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) normals[NL == RTI_NORMAL_PLANAR ? (int64_t)i * P + p : p * 3 + i] = o.n[i];
+    if (kind) kind[p] = o.kind;
+    if (peak) peak[p] = o.peak;
+  }
+}
+
+template <typename TC, int CL, typename TO, int MODE>
+__global__ void __launch_bounds__(256)
+relight_enhanced_k(const TC* __restrict__ coef, int64_t P, int vec, Enhance q, TO* __restrict__ out) {
+  constexpr int SLAB = slab_v4<TC, CL, false>();
+  __shared__ floatx4 slabs[4 * SLAB];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
+  if (wave_px >= P) return;
+  if (vec && wave_px + 256 <= P) {  // wave-uniform
+    double a[4][K];
+    load_wave<TC, CL>(coef, P, wave_px, lane, slabs + wave * SLAB, a);
+    typedef TO vec_t __attribute__((ext_vector_type(4)));
+    vec_t o;
+#pragma unroll
+    for (int v = 0; v < 4; ++v) o[v] = cvt_out<TO>(enhanced_value<MODE>(a[v], q));
+    *reinterpret_cast<vec_t*>(out + wave_px + 4 * lane) = o;
+    return;
+  }
+  for (int j = 0; j < 4; ++j) {
+    const int64_t p = wave_px + 64 * j + lane;
+    if (p >= P) break;
+    double a[K];
+    load_pixel<TC, CL>(coef, P, p, a);
+    out[p] = cvt_out<TO>(enhanced_value<MODE>(a, q));
+  }
+}
+
+// ---- launchers ------------------------------------------------------------------------------------------------
+
+struct NormalsArgs {
+  const void* coef;
+  int64_t P;
+  int vec;
+  float* normals;
+  uint8_t* kind;
+  float* peak;
+  hipStream_t s;
+};
+
+template <typename TC, int CL, int NL>
+void launch_normals_t(const NormalsArgs& a) {
+  hipLaunchKernelGGL((ptm_normals_k<TC, CL, NL>), dim3(grid_1d(a.P, 1024)), dim3(256), 0, a.s,
+                     static_cast<const TC*>(a.coef), a.P, a.vec, a.normals, a.kind, a.peak);
+}
+
+template <typename TC, int CL>
+void launch_normals_nl(const NormalsArgs& a, int nl) {
+  if (nl == RTI_NORMAL_PLANAR)
+    launch_normals_t<TC, CL, RTI_NORMAL_PLANAR>(a);
+  else
+    launch_normals_t<TC, CL, RTI_NORMAL_PIXEL_MAJOR>(a);
+}
+
+template <typename TC>
+void launch_normals_cl(const NormalsArgs& a, int cl, int nl) {
+  if (cl == RTI_COEF_PLANAR)
+    launch_normals_nl<TC, RTI_COEF_PLANAR>(a, nl);
+  else
+    launch_normals_nl<TC, RTI_COEF_PIXEL_MAJOR>(a, nl);
+}
+
+struct EnhanceArgs {
+  const void* coef;
+  int64_t P;
+  int vec;
+  Enhance q;
+  void* out;
+  hipStream_t s;
+};
+
+template <typename TC, int CL, typename TO>
+void launch_enhanced_t(const EnhanceArgs& a, int mode) {
+  const dim3 grid(grid_1d(a.P, 1024));
+  const TC* coef = static_cast<const TC*>(a.coef);
+  TO* out = static_cast<TO*>(a.out);
+  if (mode == RTI_ENHANCE_SPECULAR)
+    hipLaunchKernelGGL((relight_enhanced_k<TC, CL, TO, RTI_ENHANCE_SPECULAR>), grid, dim3(256), 0, a.s, coef, a.P, a.vec,
+                       a.q, out);
+  else
+    hipLaunchKernelGGL((relight_enhanced_k<TC, CL, TO, RTI_ENHANCE_DIFFUSE_GAIN>), grid, dim3(256), 0, a.s, coef, a.P,
+                       a.vec, a.q, out);
+}
+
+template <typename TC, int CL>
+void launch_enhanced_out(const EnhanceArgs& a, int mode, int odt) {
+  switch (odt) {
+    case RTI_F32: launch_enhanced_t<TC, CL, float>(a, mode); break;
+    case RTI_I32: launch_enhanced_t<TC, CL, int32_t>(a, mode); break;
+    default: launch_enhanced_t<TC, CL, uint8_t>(a, mode); break;
+  }
+}
+
+template <typename TC>
+void launch_enhanced_cl(const EnhanceArgs& a, int cl, int mode, int odt) {
+  if (cl == RTI_COEF_PLANAR)
+    launch_enhanced_out<TC, RTI_COEF_PLANAR>(a, mode, odt);
+  else
+    launch_enhanced_out<TC, RTI_COEF_PIXEL_MAJOR>(a, mode, odt);
+}
+
+// the checks the two entries share, in the order include/rti.h documents them
+int check_ptm_map(const char* entry, int64_t P, int coef_layout) {
+  if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", entry);
+  return check_coef_layout(entry, coef_layout);
+}
+
+int check_ptm_types(const char* entry, int basis, int coef_dtype) {
+  if (basis != RTI_BASIS_PTM6)
+    return fail(RTI_ERR_UNSUPPORTED, "%s: basis %d (PTM-6 only: HSH has no closed-form maximum)", entry, basis);
+  if (coef_dtype != RTI_F32 && coef_dtype != RTI_F64) return fail(RTI_ERR_UNSUPPORTED, "%s: coef dtype %d", entry, coef_dtype);
+  return RTI_OK;
+}
+
+}  // namespace
+}  // namespace rti
+
+using namespace rti;
+
+extern "C" int rti_ptm_normals(const void* coef, int coef_dtype, int basis, int coef_layout, int64_t P, float* normals,
+                               int normal_layout, uint8_t* kind, float* peak, rti_stream_t stream) {
+  const char* const E = "rti_ptm_normals";
+  if (int st = check_pointers(E, {coef, normals})) return st;
+  if (int st = check_ptm_map(E, P, coef_layout)) return st;
+  if (normal_layout != RTI_NORMAL_PIXEL_MAJOR && normal_layout != RTI_NORMAL_PLANAR)
+    return fail(RTI_ERR_BAD_ARG, "%s: normal layout %d", E, normal_layout);
+  if (int st = check_ptm_types(E, basis, coef_dtype)) return st;
+  const bool vec = P % 4 == 0 && aligned_to(coef, 16) && aligned_to(normals, 16) && (!kind || aligned_to(kind, 4)) &&
+                   (!peak || aligned_to(peak, 16));
+  const NormalsArgs a{coef, P, vec ? 1 : 0, normals, kind, peak, (hipStream_t)stream};
+  if (coef_dtype == RTI_F64)
+    launch_normals_cl<double>(a, coef_layout, normal_layout);
+  else
+    launch_normals_cl<float>(a, coef_layout, normal_layout);
+  return check_launch(E);
+}
+
+extern "C" int rti_relight_enhanced(const void* coef, int coef_dtype, int basis, int coef_layout, int64_t P, int mode,
+                                    double gain, double kd, double ks, int spec_exp, double lu, double lv, void* out,
+                                    int out_dtype, rti_stream_t stream) {
+  const char* const E = "rti_relight_enhanced";
+  if (int st = check_pointers(E, {coef, out})) return st;
+  if (int st = check_ptm_map(E, P, coef_layout)) return st;
+  if (mode != RTI_ENHANCE_DIFFUSE_GAIN && mode != RTI_ENHANCE_SPECULAR) return fail(RTI_ERR_BAD_ARG, "%s: mode %d", E, mode);
+  if (!std::isfinite(lu) || !std::isfinite(lv)) return fail(RTI_ERR_BAD_ARG, "%s: non-finite light direction", E);
+  if (!std::isfinite(gain) || !std::isfinite(kd) || !std::isfinite(ks))
+    return fail(RTI_ERR_BAD_ARG, "%s: non-finite gain, kd or ks", E);
+  if (gain < 0.0) return fail(RTI_ERR_BAD_ARG, "%s: gain %g < 0", E, gain);
+  if (mode == RTI_ENHANCE_SPECULAR && (spec_exp < 1 || spec_exp > 255))
+    return fail(RTI_ERR_BAD_ARG, "%s: spec_exp %d outside [1, 255]", E, spec_exp);
+  if (int st = check_ptm_types(E, basis, coef_dtype)) return st;
+  if (out_dtype != RTI_F32 && out_dtype != RTI_I32 && out_dtype != RTI_U8)
+    return fail(RTI_ERR_UNSUPPORTED, "%s: out dtype %d", E, out_dtype);
+  // the half vector between the light (lu, lv, lw) and the viewer (0, 0, 1): wave-uniform, so formed here
+  const double lw2 = 1.0 - lu * lu - lv * lv;
+  const double hz = (lw2 > 0.0 ? std::sqrt(lw2) : 0.0) + 1.0;
+  const double hn = std::sqrt(lu * lu + lv * lv + hz * hz);
+  const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // bytes of a lane's 4 outputs
+  const bool vec = P % 4 == 0 && aligned_to(coef, 16) && aligned_to(out, ovec);
+  const EnhanceArgs a{coef, P, vec ? 1 : 0, Enhance{gain, kd, ks, spec_exp, lu, lv, lu / hn, lv / hn, hz / hn}, out,
+                      (hipStream_t)stream};
+  if (coef_dtype == RTI_F64)
+    launch_enhanced_cl<double>(a, coef_layout, mode, out_dtype);
+  else
+    launch_enhanced_cl<float>(a, coef_layout, mode, out_dtype);
+  return check_launch(E);
+}

@@ -10,6 +10,9 @@ bara96/Smartphone-based-RTI: analysis.py:196-411, interactive_relighting.py:11-3
     for frame, u, v in frames: acc.add(frame, u, v)
     coef, res = acc.solve()                          # any time: a preview, add() may go on
 
+    n = rti.normals(coef)                            # [H, W, 3]: where each pixel's PTM peaks
+    img = rti.relight_enhanced(coef, 0.3, -0.2, "specular", kd=0.4, ks=150, exp=75)
+
 Compute runs in HIP kernels of librti.so (include/rti.h); importing this
 package does not touch the GPU.
 """
@@ -19,7 +22,7 @@ from .api import (BASES, FitAccumulator, apply_operator, basis_eval, basis_id, b
                   design_matrix, fit, fit_accum_solve_into, fit_accumulate_into, fit_chunked, fit_residual, fit_robust, fit_robust_into, fit_shared_into, fit_shared_residual_into, fit_with_residual,
                   gram_inverse,
                   interpolate_rbf, interpolate_rbf_perpixel, light_dirs, lsq_factors, pinv, q8_operator, h16_operator, rbf_operator,
-                  relight, relight_frame)
+                  normals, ptm_normals_into, relight, relight_enhanced, relight_enhanced_into, relight_frame)
 
 __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_into", "fit_chunked",
            "RTIError", "RTILibraryMissing", "apply_operator", "basis_eval", "basis_id", "basis_operator",
@@ -27,7 +30,8 @@ __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_in
            "fit_shared_residual_into",
            "fit_with_residual", "gram_inverse", "interpolate_rbf", "interpolate_rbf_perpixel", "light_dirs",
            "lsq_factors", "pinv", "q8_operator", "h16_operator",
-           "rbf_operator", "relight", "relight_frame", "library_path", "load"]
+           "rbf_operator", "relight", "relight_frame", "normals", "ptm_normals_into", "relight_enhanced",
+           "relight_enhanced_into", "library_path", "load"]
 
 __version__ = "0.1.0"
 

@@ -35,6 +35,11 @@ RTI_COEF_PLANAR = 1
 RTI_OUT_EVAL_MAJOR = 0
 RTI_OUT_PIXEL_MAJOR = 1
 
+RTI_NORMAL_PIXEL_MAJOR = 0  # rti_ptm_normals: normals[p][3]
+RTI_NORMAL_PLANAR = 1  # normals[3][p]
+RTI_ENHANCE_DIFFUSE_GAIN = 1  # rti_relight_enhanced modes
+RTI_ENHANCE_SPECULAR = 2
+
 RTI_KERNEL_AUTO = 0
 RTI_KERNEL_VALU = 1
 RTI_KERNEL_MFMA = 2
@@ -144,6 +149,10 @@ SIGNATURES = {
                              _c_int, _c_void_p]),
     "rti_relight_frame": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_i64, _c_double, _c_double, _c_void_p,
                                    _c_void_p, _c_void_p]),
+    "rti_ptm_normals": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_i64, _c_void_p, _c_int, _c_void_p, _c_void_p,
+                                 _c_void_p]),
+    "rti_relight_enhanced": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_double, _c_double,
+                                      _c_double, _c_int, _c_double, _c_double, _c_void_p, _c_int, _c_void_p]),
 }
 
 _lock = threading.Lock()

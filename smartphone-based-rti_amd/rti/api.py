@@ -316,6 +316,17 @@ def _unflatten(t, spatial, lead, layout=None):
     return out if lead else out[0]
 
 
+def _coef_spatial(coef, k, cl):
+    """The spatial shape of coefficient maps [..., k] (pixel-major) or [k, ...] (planar)."""
+    if cl == L.RTI_COEF_PIXEL_MAJOR:
+        if coef.shape[-1] != k:
+            raise ValueError(f"coef last dim {coef.shape[-1]} != {k} terms")
+        return tuple(coef.shape[:-1])
+    if coef.shape[0] != k:
+        raise ValueError(f"coef first dim {coef.shape[0]} != {k} terms")
+    return tuple(coef.shape[1:])
+
+
 def fit_shared_into(pinv_dev, I, coef, *, k, layout="pixel", kernel="auto", nontemporal=False, flags=0):
     """Launch ``rti_fit_shared`` on preallocated tensors (no allocation, graph-capturable).
 
@@ -852,14 +863,7 @@ def relight(coef, lu, lv, basis="ptm", *, layout="pixel", out_dtype=torch.float3
     odt = _OUT_DTYPES.get(out_dtype)
     if odt is None:
         raise ValueError("out_dtype must be float32, float64, int32 or uint8")
-    if cl == L.RTI_COEF_PIXEL_MAJOR:
-        if coef.shape[-1] != k:
-            raise ValueError(f"coef last dim {coef.shape[-1]} != {k} terms")
-        spatial = tuple(coef.shape[:-1])
-    else:
-        if coef.shape[0] != k:
-            raise ValueError(f"coef first dim {coef.shape[0]} != {k} terms")
-        spatial = tuple(coef.shape[1:])
+    spatial = _coef_spatial(coef, k, cl)
     P = int(np.prod(spatial))
     scalar = np.ndim(lu) == 0 and np.ndim(lv) == 0
     luv = np.stack([np.asarray(lu, np.float64).ravel(), np.asarray(lv, np.float64).ravel()], -1)
@@ -918,6 +922,133 @@ def relight_frame(src, hsv, lu=None, lv=None, basis="ptm", *, layout="pixel", ou
     st = L.lib().rti_relight_frame(_vp(c), sdt, b, cl, P, u, v, _vp(h), _vp(out), _stream_of(h))
     L.check(st, "rti_relight_frame")
     return out
+
+
+# ---- PTM surface normals and enhanced relighting (rti_normals.hip) ------------
+
+# the normal layouts carry the coefficient layouts' values ([p][·] = 0, [·][p] = 1; tests/test_normals_abi.py), so
+# _coef_empty and _unflatten shape a normal map as they shape 3-term coefficients
+_NORMAL_LAYOUTS = {"pixel": L.RTI_NORMAL_PIXEL_MAJOR, "pixel_major": L.RTI_NORMAL_PIXEL_MAJOR,
+                   "planar": L.RTI_NORMAL_PLANAR, L.RTI_NORMAL_PIXEL_MAJOR: L.RTI_NORMAL_PIXEL_MAJOR,
+                   L.RTI_NORMAL_PLANAR: L.RTI_NORMAL_PLANAR}
+ENHANCE_MODES = {"diffuse_gain": L.RTI_ENHANCE_DIFFUSE_GAIN, "specular": L.RTI_ENHANCE_SPECULAR}
+_ENHANCED_DTYPES = {torch.float32: L.RTI_F32, torch.int32: L.RTI_I32, torch.uint8: L.RTI_U8}
+
+
+def _normal_layout_id(layout):
+    try:
+        return _NORMAL_LAYOUTS[layout]
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown normal layout {layout!r} (expected 'pixel' or 'planar')") from None
+
+
+def _enhance_mode_id(mode):
+    if isinstance(mode, int):
+        return mode
+    try:
+        return ENHANCE_MODES[mode]
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown mode {mode!r} (expected one of {sorted(ENHANCE_MODES)})") from None
+
+
+def _ptm_maps(coef, k):
+    """Contiguous CUDA fp32 / fp64 coefficient maps of k terms per pixel -> (dtype id, P)."""
+    _require_cuda(coef, "coef")
+    cdt = _COEF_DTYPES.get(coef.dtype)
+    if cdt is None:
+        raise ValueError("coef must be float32 or float64")
+    if not coef.is_contiguous() or coef.numel() == 0 or coef.numel() % k:
+        raise ValueError(f"coef must be contiguous maps of {k} terms per pixel; got {tuple(coef.shape)}")
+    return cdt, coef.numel() // k
+
+
+def _map_out(t, name, dtype, n, like):
+    """A caller-allocated output: contiguous, ``dtype``, n elements, on the coefficients' device."""
+    _require_cuda(t, name)
+    if t.dtype != dtype or t.numel() != n or not t.is_contiguous() or t.device != like.device:
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of {n} elements on {like.device}; got "
+                         f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    return _vp(t)
+
+
+def ptm_normals_into(coef, normals, kind=None, peak=None, *, layout="pixel", normal_layout="pixel", basis="ptm"):
+    """Launch ``rti_ptm_normals`` on preallocated tensors (no allocation, graph-capturable).
+
+    coef: contiguous CUDA fp32 / fp64 maps, [P, 6] (layout="pixel") or [6, P] ("planar"), any spatial shape in
+    place of P; normals: fp32 with 3 values per pixel, [P, 3] (normal_layout="pixel") or [3, P]; kind: uint8
+    [P] or None; peak: fp32 [P] or None."""
+    b = basis_id(basis)
+    cdt, P = _ptm_maps(coef, basis_terms(b))
+    st = L.lib().rti_ptm_normals(_vp(coef), cdt, b, _layout_id(layout), P,
+                                 _map_out(normals, "normals", torch.float32, 3 * P, coef),
+                                 _normal_layout_id(normal_layout),
+                                 None if kind is None else _map_out(kind, "kind", torch.uint8, P, coef),
+                                 None if peak is None else _map_out(peak, "peak", torch.float32, P, coef),
+                                 _stream_of(coef))
+    L.check(st, "rti_ptm_normals")
+    return normals
+
+
+def relight_enhanced_into(coef, lu, lv, mode, out, *, gain=1.0, kd=1.0, ks=0.0, exp=1, layout="pixel", basis="ptm"):
+    """Launch ``rti_relight_enhanced`` on preallocated tensors (no allocation, graph-capturable).
+
+    coef as ``ptm_normals_into``; out: fp32, int32 or uint8 with one element per pixel; mode "diffuse_gain"
+    or "specular" (or the RTI_ENHANCE_* value)."""
+    b = basis_id(basis)
+    cdt, P = _ptm_maps(coef, basis_terms(b))
+    odt = _ENHANCED_DTYPES.get(out.dtype) if torch.is_tensor(out) else None
+    if odt is None:
+        raise ValueError("out must be a float32, int32 or uint8 tensor")
+    st = L.lib().rti_relight_enhanced(_vp(coef), cdt, b, _layout_id(layout), P, _enhance_mode_id(mode), float(gain),
+                                      float(kd), float(ks), int(exp), float(lu), float(lv),
+                                      _map_out(out, "out", out.dtype, P, coef), odt, _stream_of(coef))
+    L.check(st, "rti_relight_enhanced")
+    return out
+
+
+def normals(coef, *, layout="pixel", normal_layout="pixel", return_kind=False, return_peak=False, basis="ptm"):
+    """Per-pixel surface normals of PTM-6 coefficient maps on the GPU (``rti_ptm_normals``): the light
+    direction at which each pixel's fitted biquadratic peaks (Malzbender et al. 2001), in fp64 per pixel.
+
+    coef: CUDA fp32/fp64, [H, W, 6] / [P, 6] (layout="pixel") or [6, H, W] / [6, P] ("planar").  Returns
+    fp32 unit normals [H, W, 3] (normal_layout="pixel") or [3, H, W] ("planar"); with return_kind also
+    uint8 [H, W] (0 interior maximum, 1 maximum outside the unit disc, projected onto its edge, 2 no
+    maximum: the Lambertian reading of the linear terms, 4 non-finite coefficients: NaN normal); with
+    return_peak also fp32 [H, W], the PTM's value at the normal (an albedo proxy).  Only PTM-6 has a
+    closed-form maximum: any other basis raises NotImplementedError."""
+    _require_cuda(coef, "coef")
+    b = basis_id(basis)
+    cl, nl = _layout_id(layout), _normal_layout_id(normal_layout)
+    spatial = _coef_spatial(coef, basis_terms(b), cl)
+    P = int(np.prod(spatial))
+    n = _coef_empty(1, P, 3, nl, torch.float32, coef.device)
+    kind = torch.empty((1, P), dtype=torch.uint8, device=coef.device) if return_kind else None
+    peak = torch.empty((1, P), dtype=torch.float32, device=coef.device) if return_peak else None
+    ptm_normals_into(coef.contiguous(), n, kind, peak, layout=cl, normal_layout=normal_layout, basis=b)
+    out = (_unflatten(n, spatial, False, nl),) + tuple(_unflatten(t, spatial, False) for t in (kind, peak)
+                                                       if t is not None)
+    return out if len(out) > 1 else out[0]
+
+
+def relight_enhanced(coef, lu, lv, mode, *, gain=1.0, kd=1.0, ks=0.0, exp=1, layout="pixel",
+                     out_dtype=torch.float32, basis="ptm"):
+    """One enhanced rendering of PTM-6 coefficient maps at the light direction (lu, lv) on the GPU
+    (``rti_relight_enhanced``; Malzbender et al. 2001), computed from the coefficients alone.
+
+    mode="diffuse_gain": each pixel's curvature scaled by ``gain`` (>= 0) about its peak, whose location and
+    height stay (gain=1 is ``relight``).  mode="specular": kd·L(lu, lv) + ks·max(0, n·H)^exp with n the pixel's
+    normal (``normals``), H the half vector between the light and the viewer and exp an integer in [1, 255]
+    (kd=1, ks=0 is ``relight``).  coef as ``normals``.  Returns the spatial shape in out_dtype: float32, or
+    int32 / uint8 converted as ``relight`` does; an int32 result is a valid ``src`` of ``relight_frame``."""
+    _require_cuda(coef, "coef")
+    b = basis_id(basis)
+    cl = _layout_id(layout)
+    spatial = _coef_spatial(coef, basis_terms(b), cl)
+    if out_dtype not in _ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    out = torch.empty((1, int(np.prod(spatial))), dtype=out_dtype, device=coef.device)
+    relight_enhanced_into(coef.contiguous(), lu, lv, mode, out, gain=gain, kd=kd, ks=ks, exp=exp, layout=cl, basis=b)
+    return _unflatten(out, spatial, False)
 
 
 # ---- light operators (RBF, fused PTM/HSH fit + evaluation) ----------------------------------

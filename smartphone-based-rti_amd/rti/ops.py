@@ -1,5 +1,6 @@
 """PyTorch custom ops over the C ABI: ``torch.ops.rti.fit_shared`` / ``fit_shared_residual`` /
-``fit_robust`` / ``fit_accumulate`` / ``fit_accum_solve`` / ``fit_residual`` / ``relight``.
+``fit_robust`` / ``fit_accumulate`` / ``fit_accum_solve`` / ``fit_residual`` / ``relight`` / ``ptm_normals`` /
+``relight_enhanced``.
 
 They let the fit and relight kernels sit inside torch programs (and
 ``torch.library`` fake-tensor tracing) while the compute stays in librti's
@@ -240,3 +241,53 @@ def relight(coef: torch.Tensor, luv: torch.Tensor, basis: int = L.RTI_BASIS_PTM6
 @relight.register_fake
 def _(coef, luv, basis=L.RTI_BASIS_PTM6):
     return coef.new_empty((luv.shape[0], coef.shape[0]))
+
+
+def _ptm_pixels(coef, planar):
+    """P of PTM-6 maps [P, 6] (or [6, P] if planar)."""
+    if coef.dim() != 2 or coef.shape[0 if planar else 1] != 6:
+        raise ValueError(f"coef must be {'[6, P]' if planar else '[P, 6]'}; got {tuple(coef.shape)}")
+    return coef.shape[1 if planar else 0]
+
+
+@torch.library.custom_op("rti::ptm_normals", mutates_args=())
+def ptm_normals(coef: torch.Tensor, planar: bool = False,
+                normals_planar: bool = False) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Surface normals of PTM-6 maps (``rti_ptm_normals``).  coef CUDA fp32/fp64 [P, 6] (or [6, P] if planar) ->
+    ``(normals, kind, peak)``: normals fp32 [P, 3] (or [3, P] if normals_planar), kind uint8 [P], peak fp32 [P]."""
+    api._require_cuda(coef, "coef")
+    P = _ptm_pixels(coef, planar)
+    normals = coef.new_empty((3, P) if normals_planar else (P, 3), dtype=torch.float32)
+    kind = coef.new_empty((P,), dtype=torch.uint8)
+    peak = coef.new_empty((P,), dtype=torch.float32)
+    api.ptm_normals_into(coef.contiguous(), normals, kind, peak, layout="planar" if planar else "pixel",
+                         normal_layout="planar" if normals_planar else "pixel")
+    return normals, kind, peak
+
+
+@ptm_normals.register_fake
+def _(coef, planar=False, normals_planar=False):
+    P = coef.shape[1 if planar else 0]
+    return (coef.new_empty((3, P) if normals_planar else (P, 3), dtype=torch.float32),
+            coef.new_empty((P,), dtype=torch.uint8), coef.new_empty((P,), dtype=torch.float32))
+
+
+@torch.library.custom_op("rti::relight_enhanced", mutates_args=())
+def relight_enhanced(coef: torch.Tensor, lu: float, lv: float, mode: int, gain: float = 1.0, kd: float = 1.0,
+                     ks: float = 0.0, exp: int = 1, planar: bool = False,
+                     out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """One enhanced rendering of PTM-6 maps at (lu, lv) (``rti_relight_enhanced``).  coef CUDA fp32/fp64 [P, 6]
+    (or [6, P] if planar), mode RTI_ENHANCE_DIFFUSE_GAIN (1) or RTI_ENHANCE_SPECULAR (2) -> [P] in out_dtype
+    (float32, int32 or uint8)."""
+    api._require_cuda(coef, "coef")
+    P = _ptm_pixels(coef, planar)
+    if out_dtype not in api._ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    out = coef.new_empty((P,), dtype=out_dtype)
+    return api.relight_enhanced_into(coef.contiguous(), lu, lv, mode, out, gain=gain, kd=kd, ks=ks, exp=exp,
+                                     layout="planar" if planar else "pixel")
+
+
+@relight_enhanced.register_fake
+def _(coef, lu, lv, mode, gain=1.0, kd=1.0, ks=0.0, exp=1, planar=False, out_dtype=torch.float32):
+    return coef.new_empty((coef.shape[1 if planar else 0],), dtype=out_dtype)
