@@ -548,6 +548,61 @@ int rti_relight_enhanced(const void* coef, int coef_dtype, int basis, int coef_l
                          int mode, double gain, double kd, double ks, int spec_exp,
                          double lu, double lv, void* out, int out_dtype, rti_stream_t stream);
 
+/* ---- device: unsharp masking of k-channel maps, shading from a normal map (rti_unsharp.hip) ----
+ * The spatial operator of the classic RTI rendering modes (image, luminance, coefficient and normal unsharp
+ * masking); the reference has none, so these semantics are build-defined.  Relighting is
+ * linear in the coefficients, so the unsharp-masked coefficient map relights to the unsharp-masked image at
+ * every light direction, before any integer conversion.
+ * rti_gauss_radius (host): max(1, ceil(3·sigma)), or -1 for sigma not finite or <= 0.
+ * rti_gauss_taps (host): taps[0..radius], fp64: e_d = exp(−d²/(2σ²)) for d = 0..radius,
+ *   Z = e_0 + 2·Σ_{d>=1} e_d summed with d ascending, taps[d] = e_d/Z.  RTI_ERR_BAD_ARG: null taps, sigma not
+ *   finite or <= 0, radius outside [1, RTI_UNSHARP_MAX_RADIUS].
+ * rti_map_unsharp: src / dst: device fp32, dense, layout RTI_COEF_PIXEL_MAJOR ([y][x][c]) or RTI_COEF_PLANAR
+ *   ([c][y][x]), channels in [1, 16].  radius 0 = rti_gauss_radius(sigma); the effective radius R must lie in
+ *   [1, RTI_UNSHARP_MAX_RADIUS].  A pixel is valid (m = 1) when all of its channels are finite.  With
+ *   w = taps and all arithmetic in fp64 (fma where written, every other operation rounded, no contraction):
+ *     hnum_c[y][x] = Σ_{dx=−R..R ascending; 0<=x+dx<W; m[y][x+dx]} fma(w|dx|, v_c[y][x+dx], ·)
+ *     hden[y][x]   = the same sum of w|dx|
+ *     num_c[y][x]  = Σ_{dy=−R..R ascending; 0<=y+dy<H} fma(w|dy|, hnum_c[y+dy][x], ·)     den likewise from hden
+ *     blur_c = num_c/den;   o_c = v_c + amount·(v_c − blur_c);   dst_c = (float)o_c
+ *   A normalised convolution: taps outside the image and invalid pixels are left out of numerator and
+ *   denominator alike (no border replication, NaN does not spread); den >= w0² > 0 at every valid pixel.
+ *   An invalid pixel's channels are copied to dst unchanged, bit for bit.  amount = −1 is the plain blur,
+ *   amount = 0 returns src.  renorm != 0 (channels == 3): a valid pixel writes o/‖o‖ with ‖o‖ in fp64 from
+ *   the unrounded o (squares summed left to right), and (0, 0, 1) when ‖o‖ is 0 or not finite.  Every
+ *   output's sums have a fixed order: the result does not depend on the tiling, the layout or the load path,
+ *   to the bit.  One launch: a workgroup stages its 32×64 tile plus R pixels of halo per side into LDS with
+ *   the mask, runs the horizontal pass LDS -> LDS in fp64 and the vertical pass into registers; no
+ *   intermediate map goes to HBM.  16- (or 8-) byte loads need W % 4 == 0 and src 16-byte aligned (planar)
+ *   or channels % 4 (% 2) == 0 and src 16- (8-) byte aligned (pixel-major); anything else loads one float at
+ *   a time with the same arithmetic and bits.
+ * rti_shade_normals: one image out[P] from a normal map (normal_layout as rti_ptm_normals) and an optional
+ *   albedo map (fp32 [P], NULL = 1) at the light direction (lu, lv): lw = sqrt(max(0, 1 − lu² − lv²)),
+ *   l = (lu, lv, lw), H = (lu, lv, lw + 1)/‖·‖, both formed on the host in fp64 exactly as
+ *   rti_relight_enhanced forms them;
+ *     out = kd·albedo·max(0, n·l) + ks·max(0, n·H)^spec_exp
+ *   in fp64 without contraction, products and sums left to right, the power by rti_relight_enhanced's
+ *   repeated squaring.  A pixel with a NaN normal component or a NaN albedo gives NaN.  out_dtype F32 / I32 /
+ *   U8 converts as rti_relight does.  The vector path (one lane = 4 pixels) needs P % 4 == 0, normals and
+ *   albedo 16-byte aligned and out aligned to a lane's 4 elements; anything else runs one pixel per lane
+ *   with the same arithmetic and bits.
+ * Both device entries: device pointers, stream-ordered, no allocation, no synchronisation; the taps travel as
+ * kernel arguments, so the calls can be captured in a hipGraph.  Every argument check answers before any HIP
+ * call.  RTI_ERR_BAD_ARG: null src / dst / normals / out; H, W or P < 1; H·W·channels >= 2^31; channels
+ * outside [1, 16]; a bad layout; sigma not finite or <= 0; an effective radius outside [1, 32]; amount not
+ * finite; renorm with channels != 3; src and dst ranges that overlap; non-finite kd, ks, lu or lv; spec_exp
+ * outside [1, 255].  RTI_ERR_UNSUPPORTED: an out_dtype other than F32 / I32 / U8.
+ * Not built: halo exchange between the row tiles of a multi-GPU map, fp64 maps, strided maps. */
+#define RTI_UNSHARP_MAX_RADIUS 32
+int rti_gauss_radius(double sigma);
+int rti_gauss_taps(double sigma, int radius, double* taps);
+int rti_map_unsharp(const float* src, int channels, int layout, int H, int W,
+                    double sigma, int radius, double amount, int renorm,
+                    float* dst, rti_stream_t stream);
+int rti_shade_normals(const float* normals, int normal_layout, const float* albedo /* NULL = 1 */, int64_t P,
+                      double kd, double ks, int spec_exp, double lu, double lv,
+                      void* out, int out_dtype, rti_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

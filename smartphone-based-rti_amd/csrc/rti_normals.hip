@@ -33,6 +33,7 @@
 #include <type_traits>
 
 #include "rti_convert.h"
+#include "rti_shade.h"
 #include "rti_stack.h"
 
 namespace rti {
@@ -118,18 +119,6 @@ __device__ __forceinline__ double diffuse_gain_value(const double (&a)[K], const
 #pragma unroll
   for (int i = 0; i < K; ++i) b[i] = k.has_max ? b[i] : a[i];
   return k.finite ? ptm_value(b, lu, lv) : (double)NAN;
-}
-
-// x^e, 1 <= e <= 255, by repeated squaring (e is wave-uniform); no pow
-__device__ __forceinline__ double powi(double x, int e) {
-#pragma clang fp contract(off)
-  double r = 1.0, b = x;
-  for (;;) {
-    if (e & 1) r = r * b;
-    e >>= 1;
-    if (!e) return r;
-    b = b * b;
-  }
 }
 
 struct Enhance {
@@ -456,13 +445,10 @@ extern "C" int rti_relight_enhanced(const void* coef, int coef_dtype, int basis,
   if (int st = check_ptm_types(E, basis, coef_dtype)) return st;
   if (out_dtype != RTI_F32 && out_dtype != RTI_I32 && out_dtype != RTI_U8)
     return fail(RTI_ERR_UNSUPPORTED, "%s: out dtype %d", E, out_dtype);
-  // the half vector between the light (lu, lv, lw) and the viewer (0, 0, 1): wave-uniform, so formed here
-  const double lw2 = 1.0 - lu * lu - lv * lv;
-  const double hz = (lw2 > 0.0 ? std::sqrt(lw2) : 0.0) + 1.0;
-  const double hn = std::sqrt(lu * lu + lv * lv + hz * hz);
+  const LightFrame f = light_frame(lu, lv);
   const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // bytes of a lane's 4 outputs
   const bool vec = P % 4 == 0 && aligned_to(coef, 16) && aligned_to(out, ovec);
-  const EnhanceArgs a{coef, P, vec ? 1 : 0, Enhance{gain, kd, ks, spec_exp, lu, lv, lu / hn, lv / hn, hz / hn}, out,
+  const EnhanceArgs a{coef, P, vec ? 1 : 0, Enhance{gain, kd, ks, spec_exp, lu, lv, f.hx, f.hy, f.hz}, out,
                       (hipStream_t)stream};
   if (coef_dtype == RTI_F64)
     launch_enhanced_cl<double>(a, coef_layout, mode, out_dtype);

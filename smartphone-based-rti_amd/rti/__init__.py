@@ -13,6 +13,9 @@ bara96/Smartphone-based-RTI: analysis.py:196-411, interactive_relighting.py:11-3
     n = rti.normals(coef)                            # [H, W, 3]: where each pixel's PTM peaks
     img = rti.relight_enhanced(coef, 0.3, -0.2, "specular", kd=0.4, ks=150, exp=75)
 
+    sharp = rti.relight(rti.unsharp(coef, 2.0, 1.5), 0.3, -0.2)   # unsharp masking, for every light at once
+    img = rti.shade_normals(rti.normals_unsharp(n, 2.0, 1.5), 0.3, -0.2)          # enhanced normals, shaded
+
 Compute runs in HIP kernels of librti.so (include/rti.h); importing this
 package does not touch the GPU.
 """
@@ -22,7 +25,8 @@ from .api import (BASES, FitAccumulator, apply_operator, basis_eval, basis_id, b
                   design_matrix, fit, fit_accum_solve_into, fit_accumulate_into, fit_chunked, fit_residual, fit_robust, fit_robust_into, fit_shared_into, fit_shared_residual_into, fit_with_residual,
                   gram_inverse,
                   interpolate_rbf, interpolate_rbf_perpixel, light_dirs, lsq_factors, pinv, q8_operator, h16_operator, rbf_operator,
-                  normals, ptm_normals_into, relight, relight_enhanced, relight_enhanced_into, relight_frame)
+                  normals, ptm_normals_into, relight, relight_enhanced, relight_enhanced_into, relight_frame,
+                  gauss_taps, map_unsharp_into, normals_unsharp, shade_normals, shade_normals_into, unsharp)
 
 __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_into", "fit_chunked",
            "RTIError", "RTILibraryMissing", "apply_operator", "basis_eval", "basis_id", "basis_operator",
@@ -31,7 +35,8 @@ __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_in
            "fit_with_residual", "gram_inverse", "interpolate_rbf", "interpolate_rbf_perpixel", "light_dirs",
            "lsq_factors", "pinv", "q8_operator", "h16_operator",
            "rbf_operator", "relight", "relight_frame", "normals", "ptm_normals_into", "relight_enhanced",
-           "relight_enhanced_into", "library_path", "load"]
+           "relight_enhanced_into", "gauss_taps", "map_unsharp_into", "normals_unsharp", "shade_normals",
+           "shade_normals_into", "unsharp", "library_path", "load"]
 
 __version__ = "0.1.0"
 

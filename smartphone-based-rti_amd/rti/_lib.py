@@ -39,6 +39,7 @@ RTI_NORMAL_PIXEL_MAJOR = 0  # rti_ptm_normals: normals[p][3]
 RTI_NORMAL_PLANAR = 1  # normals[3][p]
 RTI_ENHANCE_DIFFUSE_GAIN = 1  # rti_relight_enhanced modes
 RTI_ENHANCE_SPECULAR = 2
+RTI_UNSHARP_MAX_RADIUS = 32  # rti_map_unsharp: the largest Gaussian radius
 
 RTI_KERNEL_AUTO = 0
 RTI_KERNEL_VALU = 1
@@ -153,6 +154,12 @@ SIGNATURES = {
                                  _c_void_p]),
     "rti_relight_enhanced": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_double, _c_double,
                                       _c_double, _c_int, _c_double, _c_double, _c_void_p, _c_int, _c_void_p]),
+    "rti_gauss_radius": (_c_int, [_c_double]),
+    "rti_gauss_taps": (_c_int, [_c_double, _c_int, _c_double_p]),
+    "rti_map_unsharp": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_int, _c_double, _c_int, _c_double, _c_int,
+                                 _c_void_p, _c_void_p]),
+    "rti_shade_normals": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_i64, _c_double, _c_double, _c_int, _c_double,
+                                   _c_double, _c_void_p, _c_int, _c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -1051,6 +1051,129 @@ def relight_enhanced(coef, lu, lv, mode, *, gain=1.0, kd=1.0, ks=0.0, exp=1, lay
     return _unflatten(out, spatial, False)
 
 
+# ---- unsharp masking of maps, shading from a normal map (rti_unsharp.hip) ------------
+
+def gauss_taps(sigma, radius=None):
+    """The normalised Gaussian taps w[0..R] ``rti_map_unsharp`` convolves with (host, fp64): w0 + 2·Σ w = 1.
+    radius None = max(1, ceil(3·sigma))."""
+    lib = L.lib()
+    R = lib.rti_gauss_radius(float(sigma)) if radius is None else int(radius)
+    if R < 0:
+        raise ValueError(f"rti_gauss_radius: sigma {sigma!r} must be finite and positive")
+    taps = np.zeros(max(R, 0) + 1, np.float64)
+    L.check(lib.rti_gauss_taps(float(sigma), R, _dptr(taps)), "rti_gauss_taps")
+    return taps
+
+
+def _map_dims(src, layout, renorm=False):
+    """A dense fp32 map [H, W], [H, W, k] (pixel-major) or [k, H, W] (planar) on the GPU -> (channels, H, W).  The
+    dtype and the shape are judged before the device, so a wrong map is named as such wherever it lives."""
+    if not torch.is_tensor(src):
+        raise ValueError("map must be a CUDA (HIP) tensor")
+    if src.dtype != torch.float32:
+        raise ValueError(f"map must be float32 (fp64 maps are not built); got {src.dtype}")
+    if src.dim() == 2:
+        k, (H, W) = 1, src.shape
+    elif src.dim() == 3:
+        k, H, W = (src.shape[2], src.shape[0], src.shape[1]) if layout == L.RTI_COEF_PIXEL_MAJOR else tuple(src.shape)
+    else:
+        raise ValueError(f"map must be [H, W], [H, W, k] (pixel) or [k, H, W] (planar); got {tuple(src.shape)}")
+    if renorm and k != 3:
+        raise ValueError(f"renorm needs 3 channels (a normal map); got {k}")
+    if not src.is_contiguous():
+        raise ValueError("map must be contiguous (strided maps are not built)")
+    _require_cuda(src, "map")
+    return int(k), int(H), int(W)
+
+
+def map_unsharp_into(src, dst, *, sigma, amount=1.0, radius=0, layout="pixel", renorm=False):
+    """Launch ``rti_map_unsharp`` on preallocated tensors (no allocation, graph-capturable).
+
+    src: contiguous CUDA fp32 [H, W], [H, W, k] (layout="pixel") or [k, H, W] ("planar"), k <= 16; dst: the
+    same shape, not overlapping src.  dst = src + amount·(src − blur) with blur the Gaussian of ``sigma``
+    cut at ``radius`` (0 = max(1, ceil(3·sigma)), at most 32), normalised over the finite pixels inside the
+    image; a pixel with a non-finite channel is copied.  renorm (k = 3): the result scaled to unit length."""
+    cl = _layout_id(layout)
+    k, H, W = _map_dims(src, cl, renorm)
+    _require_cuda(dst, "dst")
+    if dst.dtype != torch.float32 or dst.shape != src.shape or not dst.is_contiguous() or dst.device != src.device:
+        raise ValueError(f"dst must be a contiguous float32 tensor of shape {tuple(src.shape)} on {src.device}; got "
+                         f"{dst.dtype} {tuple(dst.shape)} on {dst.device}")
+    st = L.lib().rti_map_unsharp(_vp(src), k, cl, H, W, float(sigma), int(radius), float(amount), int(bool(renorm)),
+                                 _vp(dst), _stream_of(src))
+    L.check(st, "rti_map_unsharp")
+    return dst
+
+
+def unsharp(map, sigma, amount=1.0, *, radius=None, layout="pixel", renorm=False):
+    """Unsharp masking of a k-channel map on the GPU (``rti_map_unsharp``): map + amount·(map − blur).
+
+    map: CUDA fp32 [H, W], [H, W, k] (layout="pixel") or [k, H, W] ("planar"), k <= 16; returns the same
+    shape.  On coefficient maps this is unsharp masking of the relit image at every light direction at once
+    (relighting is linear in the coefficients): ``relight(unsharp(coef, s, a), lu, lv)``.  amount=-1 is the
+    plain Gaussian blur.  NaN / inf pixels (``fit_robust``, ``normals`` kind 4) are left out of their
+    neighbours' blur and copied.  radius None = max(1, ceil(3·sigma)); at most 32.  Not built: maps split
+    over GPUs (``rti.parallel`` row tiles would need a halo exchange), fp64 and strided maps."""
+    if not torch.is_tensor(map):
+        raise ValueError("map must be a CUDA (HIP) tensor")
+    src = map.contiguous()
+    return map_unsharp_into(src, torch.empty_like(src), sigma=sigma, amount=amount, radius=0 if radius is None else radius,
+                            layout=layout, renorm=renorm)
+
+
+def normals_unsharp(n, sigma, amount=1.0, **kw):
+    """Enhanced normals: ``unsharp`` of a normal map ([H, W, 3] / [3, H, W]) renormalised to unit length."""
+    return unsharp(n, sigma, amount, renorm=True, **kw)
+
+
+def shade_normals_into(n, lu, lv, out, *, albedo=None, kd=1.0, ks=0.0, exp=1, normal_layout="pixel"):
+    """Launch ``rti_shade_normals`` on preallocated tensors (no allocation, graph-capturable).
+
+    n: contiguous CUDA fp32 normals, [P, 3] (normal_layout="pixel") or [3, P], any spatial shape in place of P;
+    albedo: None or fp32 [P]; out: fp32, int32 or uint8 with one element per pixel."""
+    if not torch.is_tensor(n) or n.dtype != torch.float32 or not n.is_contiguous() or n.numel() == 0 or n.numel() % 3:
+        raise ValueError("n must be a contiguous float32 normal map of 3 values per pixel; got "
+                         f"{getattr(n, 'dtype', type(n))} {tuple(getattr(n, 'shape', ()))}")
+    _require_cuda(n, "n")
+    P = n.numel() // 3
+    odt = _ENHANCED_DTYPES.get(out.dtype) if torch.is_tensor(out) else None
+    if odt is None:
+        raise ValueError("out must be a float32, int32 or uint8 tensor")
+    st = L.lib().rti_shade_normals(_vp(n), _normal_layout_id(normal_layout),
+                                   None if albedo is None else _map_out(albedo, "albedo", torch.float32, P, n), P,
+                                   float(kd), float(ks), int(exp), float(lu), float(lv),
+                                   _map_out(out, "out", out.dtype, P, n), odt, _stream_of(n))
+    L.check(st, "rti_shade_normals")
+    return out
+
+
+def shade_normals(n, lu, lv, *, albedo=None, kd=1.0, ks=0.0, exp=1, normal_layout="pixel", out_dtype=torch.float32):
+    """One image shaded from a normal map at the light direction (lu, lv) on the GPU (``rti_shade_normals``):
+    kd·albedo·max(0, n·l) + ks·max(0, n·H)^exp with l = (lu, lv, sqrt(max(0, 1 − lu² − lv²))) and H the half
+    vector between l and the viewer.  The renderer of ``normals_unsharp``: ``relight_enhanced`` recomputes its
+    normals from the coefficients and cannot take a map.
+
+    n: CUDA fp32 [H, W, 3] / [P, 3] (normal_layout="pixel") or [3, H, W] / [3, P] ("planar"); albedo: None (1)
+    or fp32 with one value per pixel (e.g. the peak of ``normals``).  Returns the spatial shape in out_dtype
+    (float32, or int32 / uint8 converted as ``relight`` does); NaN normals or albedo give NaN."""
+    if not torch.is_tensor(n) or n.dtype != torch.float32:
+        raise ValueError(f"n must be a float32 normal map; got {getattr(n, 'dtype', type(n))}")
+    nl = _normal_layout_id(normal_layout)
+    spatial = _coef_spatial(n, 3, nl)
+    if out_dtype not in _ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    _require_cuda(n, "n")
+    P = int(np.prod(spatial))
+    if albedo is not None:
+        _require_cuda(albedo, "albedo")
+        if tuple(albedo.shape) != spatial:
+            raise ValueError(f"albedo {tuple(albedo.shape)} does not match the normal map's pixels {spatial}")
+        albedo = albedo.contiguous().reshape(P)
+    out = torch.empty((1, P), dtype=out_dtype, device=n.device)
+    shade_normals_into(n.contiguous(), lu, lv, out, albedo=albedo, kd=kd, ks=ks, exp=exp, normal_layout=nl)
+    return _unflatten(out, spatial, False)
+
+
 # ---- light operators (RBF, fused PTM/HSH fit + evaluation) ----------------------------------
 
 def _query(qu, qv):

@@ -1,6 +1,6 @@
 """PyTorch custom ops over the C ABI: ``torch.ops.rti.fit_shared`` / ``fit_shared_residual`` /
 ``fit_robust`` / ``fit_accumulate`` / ``fit_accum_solve`` / ``fit_residual`` / ``relight`` / ``ptm_normals`` /
-``relight_enhanced``.
+``relight_enhanced`` / ``map_unsharp`` / ``shade_normals``.
 
 They let the fit and relight kernels sit inside torch programs (and
 ``torch.library`` fake-tensor tracing) while the compute stays in librti's
@@ -291,3 +291,42 @@ def relight_enhanced(coef: torch.Tensor, lu: float, lv: float, mode: int, gain: 
 @relight_enhanced.register_fake
 def _(coef, lu, lv, mode, gain=1.0, kd=1.0, ks=0.0, exp=1, planar=False, out_dtype=torch.float32):
     return coef.new_empty((coef.shape[1 if planar else 0],), dtype=out_dtype)
+
+
+@torch.library.custom_op("rti::map_unsharp", mutates_args=())
+def map_unsharp(src: torch.Tensor, sigma: float, amount: float = 1.0, radius: int = 0, planar: bool = False,
+                renorm: bool = False) -> torch.Tensor:
+    """Unsharp masking of a map (``rti_map_unsharp``).  src CUDA fp32 [H, W], [H, W, k] (or [k, H, W] if planar)
+    -> the same shape; radius 0 = max(1, ceil(3·sigma)); renorm (k = 3): unit-length result."""
+    s = src.contiguous()
+    return api.map_unsharp_into(s, torch.empty_like(s), sigma=sigma, amount=amount, radius=radius,
+                                layout="planar" if planar else "pixel", renorm=renorm)
+
+
+@map_unsharp.register_fake
+def _(src, sigma, amount=1.0, radius=0, planar=False, renorm=False):
+    return src.new_empty(src.shape)
+
+
+@torch.library.custom_op("rti::shade_normals", mutates_args=())
+def shade_normals(n: torch.Tensor, lu: float, lv: float, albedo: torch.Tensor | None = None, kd: float = 1.0,
+                  ks: float = 0.0, exp: int = 1, planar: bool = False,
+                  out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """One image shaded from a normal map at (lu, lv) (``rti_shade_normals``).  n CUDA fp32 [P, 3] (or [3, P] if
+    planar), albedo None or fp32 [P] -> [P] in out_dtype (float32, int32 or uint8)."""
+    api._require_cuda(n, "n")
+    if n.dim() != 2 or n.shape[0 if planar else 1] != 3:
+        raise ValueError(f"n must be {'[3, P]' if planar else '[P, 3]'}; got {tuple(n.shape)}")
+    if albedo is not None:
+        api._require_cuda(albedo, "albedo")
+        _same_device(n=n, albedo=albedo)
+    if out_dtype not in api._ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    out = n.new_empty((n.shape[1 if planar else 0],), dtype=out_dtype)
+    return api.shade_normals_into(n.contiguous(), lu, lv, out, albedo=None if albedo is None else albedo.contiguous(),
+                                  kd=kd, ks=ks, exp=exp, normal_layout="planar" if planar else "pixel")
+
+
+@shade_normals.register_fake
+def _(n, lu, lv, albedo=None, kd=1.0, ks=0.0, exp=1, planar=False, out_dtype=torch.float32):
+    return n.new_empty((n.shape[1 if planar else 0],), dtype=out_dtype)
