@@ -603,6 +603,49 @@ int rti_shade_normals(const float* normals, int normal_layout, const float* albe
                       double kd, double ks, int spec_exp, double lu, double lv,
                       void* out, int out_dtype, rti_stream_t stream);
 
+/* ---- device: LRGB PTMs, the colour form (rti_lrgb.hip) ------------------------------------------
+ * Six luminance coefficients and one RGB colour per pixel, rendered as rgb · L(lu, lv): the form in which
+ * Malzbender, Gelb and Wolters (2001) and every PTM viewer hold a colour object, and one of the two
+ * uncompressed payloads of the .ptm format.  The reference fits one channel, so these semantics are
+ * build-defined.  PTM-6 only: the entries take no basis argument, and the Python layer
+ * answers any other basis with NotImplementedError (RTI_ERR_UNSUPPORTED's exception).
+ * An LRGB map is fp32 with 9 channels (a0..a5, cR, cG, cB), [p][9] (RTI_COEF_PIXEL_MAJOR) or [9][p]
+ * (RTI_COEF_PLANAR); the first six planes of a planar map are a dense PTM-6 map that rti_ptm_normals,
+ * rti_relight_enhanced and rti_map_unsharp take as it is.
+ * rti_lrgb_from_rgb: coef: device fp32, three PTM-6 maps as rti_fit_shared writes them with C = 3
+ *   (coef_layout, coef_channel_stride in elements, 0 = dense = 6·P).  gram: HOST fp64 [6][6], AᵀA of the
+ *   shared design; weights: HOST fp64 [3] or NULL = 1.0/3.0 each (not normalised by the library).  Both are
+ *   read during the call and travel as kernel arguments, so the call can be captured in a hipGraph.  Per
+ *   pixel, in fp64 from the fp32 inputs, no contraction, every product and sum rounded, each expression
+ *   left to right as written (x_c = channel c's coefficients, r g b = x_0 x_1 x_2):
+ *     a_j = w0·r_j + w1·g_j + w2·b_j                      j = 0..5
+ *     t_i = G[i][0]·a_0 + G[i][1]·a_1 + … + G[i][5]·a_5
+ *     d   = a_0·t_0 + … + a_5·t_5
+ *     s_c = x_c,0·t_0 + … + x_c,5·t_5
+ *   any of the 18 inputs not finite: all nine outputs NaN; else d finite and d > 0: chroma_c = s_c/d; else
+ *   (a black pixel): chroma = (1, 1, 1).  Written: (float)a_j, (float)chroma_c.  chroma_c is the c that
+ *   minimises Σ_n (I_c,n − c·A_n·a)² when coef_c is the least-squares fit of I_c (AᵀI_c = G·coef_c), and
+ *   Σ_c w_c·chroma_c = 1 up to rounding whenever d > 0 (Σ_c w_c·s_c = a·t = d).
+ *   72 bytes in and 36 out per pixel.
+ * rti_relight_lrgb: luv: device fp64 [E][2] as rti_relight's; out[e][p][c], RGB interleaved.  Per pixel and
+ *   direction L = the six terms (double)a_i · b_i(lu_e, lv_e) summed as rti_relight's F64 path sums them,
+ *   channel c = (double)chroma_c · L converted once: F32 value; I32 / U8 as rti_relight (a NaN gives NaN,
+ *   INT32_MIN, 0).  With chroma = 1 the F32 output equals rti_relight's of the fp64 coefficients bit for
+ *   bit.  The map is read once for all E directions of a launch (the kernel loops over them): 36 bytes in
+ *   and 3·sizeof(out) per direction out per pixel.
+ * Both entries: device pointers but gram / weights, stream-ordered, no allocation, no synchronisation.
+ * Every argument check answers before any HIP call.  RTI_ERR_BAD_ARG: a null pointer other than weights;
+ * P < 1 (or E < 1); a bad layout; a channel stride below its dense value; a non-finite gram entry; a weight
+ * that is negative or not finite; weights that are all zero.  RTI_ERR_UNSUPPORTED: an out_dtype other than
+ * F32 / I32 / U8.  The vector path (one lane = 4 pixels) needs P % 4 == 0, the maps 16-byte aligned with a
+ * channel stride that is a multiple of 4, and out 16-byte (U8: 4-byte) aligned; anything else, and the last
+ * partial 256-pixel chunk, runs one pixel per lane with the same arithmetic and bits. */
+int rti_lrgb_from_rgb(const float* coef, int coef_layout, int64_t coef_channel_stride, int64_t P,
+                      const double* gram, const double* weights /* NULL = 1/3 each */,
+                      float* lrgb, int lrgb_layout, rti_stream_t stream);
+int rti_relight_lrgb(const float* lrgb, int lrgb_layout, int64_t P, const double* luv, int E,
+                     void* out, int out_dtype, rti_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

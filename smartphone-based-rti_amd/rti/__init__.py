@@ -16,6 +16,10 @@ bara96/Smartphone-based-RTI: analysis.py:196-411, interactive_relighting.py:11-3
     sharp = rti.relight(rti.unsharp(coef, 2.0, 1.5), 0.3, -0.2)   # unsharp masking, for every light at once
     img = rti.shade_normals(rti.normals_unsharp(n, 2.0, 1.5), 0.3, -0.2)          # enhanced normals, shaded
 
+    m = rti.fit_lrgb(Irgb, lu, lv)                   # Irgb: CUDA [3, N, H, W] -> LRGB PTM [H, W, 9]
+    rgb = rti.relight_lrgb(m, 0.3, -0.2, out_dtype=torch.uint8)   # [H, W, 3] in one launch
+    rti.write_ptm("object.ptm", m)                   # opens in a PTM viewer
+
 Compute runs in HIP kernels of librti.so (include/rti.h); importing this
 package does not touch the GPU.
 """
@@ -26,7 +30,9 @@ from .api import (BASES, FitAccumulator, apply_operator, basis_eval, basis_id, b
                   gram_inverse,
                   interpolate_rbf, interpolate_rbf_perpixel, light_dirs, lsq_factors, pinv, q8_operator, h16_operator, rbf_operator,
                   normals, ptm_normals_into, relight, relight_enhanced, relight_enhanced_into, relight_frame,
-                  gauss_taps, map_unsharp_into, normals_unsharp, shade_normals, shade_normals_into, unsharp)
+                  gauss_taps, map_unsharp_into, normals_unsharp, shade_normals, shade_normals_into, unsharp,
+                  fit_lrgb, gram, lrgb_from_rgb, lrgb_from_rgb_into, lrgb_luminance, relight_lrgb, relight_lrgb_into)
+from .io import read_ptm, write_ptm
 
 __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_into", "fit_chunked",
            "RTIError", "RTILibraryMissing", "apply_operator", "basis_eval", "basis_id", "basis_operator",
@@ -36,7 +42,8 @@ __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_in
            "lsq_factors", "pinv", "q8_operator", "h16_operator",
            "rbf_operator", "relight", "relight_frame", "normals", "ptm_normals_into", "relight_enhanced",
            "relight_enhanced_into", "gauss_taps", "map_unsharp_into", "normals_unsharp", "shade_normals",
-           "shade_normals_into", "unsharp", "library_path", "load"]
+           "shade_normals_into", "unsharp", "fit_lrgb", "gram", "lrgb_from_rgb", "lrgb_from_rgb_into",
+           "lrgb_luminance", "relight_lrgb", "relight_lrgb_into", "read_ptm", "write_ptm", "library_path", "load"]
 
 __version__ = "0.1.0"
 

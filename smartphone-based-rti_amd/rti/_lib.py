@@ -160,6 +160,9 @@ SIGNATURES = {
                                  _c_void_p, _c_void_p]),
     "rti_shade_normals": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_i64, _c_double, _c_double, _c_int, _c_double,
                                    _c_double, _c_void_p, _c_int, _c_void_p]),
+    "rti_lrgb_from_rgb": (_c_int, [_c_void_p, _c_int, _c_i64, _c_i64, _c_double_p, _c_double_p, _c_void_p, _c_int,
+                                   _c_void_p]),
+    "rti_relight_lrgb": (_c_int, [_c_void_p, _c_int, _c_i64, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -1174,6 +1174,155 @@ def shade_normals(n, lu, lv, *, albedo=None, kd=1.0, ks=0.0, exp=1, normal_layou
     return _unflatten(out, spatial, False)
 
 
+# ---- LRGB PTMs: colour fit and one-pass RGB relight (rti_lrgb.hip) ------------
+
+def gram(lu, lv):
+    """Host fp64 Gram matrix AᵀA [6, 6] of the shared PTM-6 design (``design_matrix``): with it the
+    least-squares colour of a pixel follows from its three coefficient vectors (``lrgb_from_rgb``)."""
+    A = design_matrix(lu, lv, "ptm")
+    return A.T @ A
+
+
+def _gram_host(gram):
+    g = np.ascontiguousarray(np.asarray(gram.detach().cpu() if torch.is_tensor(gram) else gram, dtype=np.float64))
+    if g.shape != (6, 6):
+        raise ValueError(f"gram must be [6, 6] (rti.gram(lu, lv)); got {g.shape}")
+    return g
+
+
+def _weights_host(weights):
+    if weights is None:
+        return None
+    w = np.ascontiguousarray(np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights,
+                                        dtype=np.float64).ravel())
+    if w.size != 3:
+        raise ValueError(f"weights must be 3 channel weights; got {w.size}")
+    return w
+
+
+def _lrgb_map(lrgb):
+    """A contiguous CUDA fp32 LRGB map of 9 values per pixel -> P."""
+    _require_cuda(lrgb, "lrgb")
+    if lrgb.dtype != torch.float32 or not lrgb.is_contiguous() or lrgb.numel() == 0 or lrgb.numel() % 9:
+        raise ValueError(f"lrgb must be a contiguous float32 map of 9 values per pixel; got {lrgb.dtype} "
+                         f"{tuple(lrgb.shape)}")
+    return lrgb.numel() // 9
+
+
+def lrgb_from_rgb_into(coef, gram, lrgb, *, weights=None, layout="pixel", lrgb_layout="pixel"):
+    """Launch ``rti_lrgb_from_rgb`` on preallocated tensors (no allocation, graph-capturable).
+
+    coef: contiguous CUDA fp32, three PTM-6 maps [3, P, 6] (layout="pixel") or [3, 6, P] ("planar"), any
+    spatial shape in place of P; gram: host fp64 [6, 6] (``gram``); weights: None (1/3 each) or 3 host
+    values; lrgb: fp32 with 9 values per pixel, [P, 9] (lrgb_layout="pixel") or [9, P]."""
+    _require_cuda(coef, "coef")
+    if coef.dtype != torch.float32 or not coef.is_contiguous() or coef.dim() < 2 or coef.shape[0] != 3 \
+            or coef.numel() == 0 or coef.numel() % 18:
+        raise ValueError(f"coef must be three contiguous float32 PTM-6 maps [3, ...]; got {coef.dtype} "
+                         f"{tuple(coef.shape)}")
+    P = coef.numel() // 18
+    g, w = _gram_host(gram), _weights_host(weights)
+    st = L.lib().rti_lrgb_from_rgb(_vp(coef), _layout_id(layout), 6 * P, P, _dptr(g), None if w is None else _dptr(w),
+                                   _map_out(lrgb, "lrgb", torch.float32, 9 * P, coef), _layout_id(lrgb_layout),
+                                   _stream_of(coef))
+    L.check(st, "rti_lrgb_from_rgb")
+    return lrgb
+
+
+def lrgb_from_rgb(coef, gram, *, weights=None, layout="pixel", lrgb_layout="pixel"):
+    """Three per-channel PTM-6 maps -> one LRGB map on the GPU (``rti_lrgb_from_rgb``): the luminance
+    coefficients a = Σ_c w_c·coef_c and, per pixel, the RGB colour that best explains the three channels as
+    colour · luminance over the lights of the fit (least squares, from the coefficients and the Gram matrix
+    alone: no second pass over the stack).
+
+    coef: CUDA fp32 [3, H, W, 6] (layout="pixel") or [3, 6, H, W] ("planar"), as ``fit`` returns it for a
+    [3, N, H, W] stack; gram: ``gram(lu, lv)`` of the fit's directions; weights: None (1/3 each) or 3
+    non-negative values (not normalised).  Returns fp32 [H, W, 9] (lrgb_layout="pixel") or [9, H, W]:
+    (a0..a5, cR, cG, cB), Σ_c w_c·chroma_c = 1; a black pixel has chroma 1, a non-finite one nine NaNs."""
+    _require_cuda(coef, "coef")
+    cl, ol = _layout_id(layout), _layout_id(lrgb_layout)
+    if coef.dim() < 2 or coef.shape[0] != 3:
+        raise ValueError(f"coef must be three PTM-6 maps [3, ...]; got {tuple(coef.shape)}")
+    spatial = _coef_spatial(coef[0], 6, cl)
+    out = _coef_empty(1, int(np.prod(spatial)), 9, ol, torch.float32, coef.device)
+    lrgb_from_rgb_into(coef.contiguous(), gram, out, weights=weights, layout=cl, lrgb_layout=ol)
+    return _unflatten(out, spatial, False, ol)
+
+
+def fit_lrgb(I, lu, lv, *, weights=None, rcond=None, lrgb_layout="pixel", **fit_kw):
+    """Fit an LRGB PTM to a colour stack on the GPU: ``fit`` of the three channels (one pass over the stack),
+    then ``lrgb_from_rgb``.
+
+    I: CUDA [3, N, H, W] light-major, any dtype ``fit`` takes; lu, lv: the N directions.  fit_kw: ``fit``'s
+    keywords (kernel, layout of the intermediate maps, ...); PTM-6, shared mode.  Returns fp32 [H, W, 9] or
+    [9, H, W] (lrgb_layout)."""
+    _require_cuda(I, "I")
+    if I.dim() != 4 or I.shape[0] != 3:
+        raise ValueError(f"I must be a colour stack [3, N, H, W]; got {tuple(I.shape)}")
+    if basis_id(fit_kw.pop("basis", "ptm")) != L.RTI_BASIS_PTM6:
+        raise NotImplementedError("rti_lrgb_from_rgb: LRGB maps are PTM-6 only")
+    if fit_kw.pop("mode", "shared") != "shared":
+        raise NotImplementedError("fit_lrgb: the Gram matrix is that of a shared light set (mode='shared')")
+    layout = fit_kw.pop("layout", "pixel")
+    coef = fit(I, lu, lv, "ptm", "shared", rcond, layout=layout, **fit_kw)
+    return lrgb_from_rgb(coef, gram(lu, lv), weights=weights, layout=layout, lrgb_layout=lrgb_layout)
+
+
+def relight_lrgb_into(lrgb, luv_dev, out, *, layout="pixel"):
+    """Launch ``rti_relight_lrgb`` on preallocated tensors (no allocation, graph-capturable).
+
+    lrgb: contiguous CUDA fp32 [P, 9] (layout="pixel") or [9, P], any spatial shape in place of P; luv_dev:
+    CUDA fp64 [E, 2]; out: float32, int32 or uint8 with E·P·3 elements ([E, P, 3], RGB interleaved)."""
+    P = _lrgb_map(lrgb)
+    _require_cuda(luv_dev, "luv")
+    if luv_dev.dtype != torch.float64 or luv_dev.dim() != 2 or luv_dev.shape[1] != 2 or luv_dev.shape[0] < 1 \
+            or not luv_dev.is_contiguous() or luv_dev.device != lrgb.device:
+        raise ValueError(f"luv must be a contiguous float64 [E, 2] tensor on {lrgb.device}; got {luv_dev.dtype} "
+                         f"{tuple(luv_dev.shape)} on {luv_dev.device}")
+    E = luv_dev.shape[0]
+    odt = _ENHANCED_DTYPES.get(out.dtype) if torch.is_tensor(out) else None
+    if odt is None:
+        raise ValueError("out must be a float32, int32 or uint8 tensor")
+    st = L.lib().rti_relight_lrgb(_vp(lrgb), _layout_id(layout), P, _vp(luv_dev), E,
+                                  _map_out(out, "out", out.dtype, E * P * 3, lrgb), odt, _stream_of(lrgb))
+    L.check(st, "rti_relight_lrgb")
+    return out
+
+
+def relight_lrgb(lrgb, lu, lv, *, layout="pixel", out_dtype=torch.float32):
+    """Relight an LRGB map to RGB images on the GPU in one launch (``rti_relight_lrgb``): per pixel
+    chroma_c · L(lu, lv), the map read once for every direction.
+
+    lrgb: CUDA fp32 [H, W, 9] / [P, 9] (layout="pixel") or [9, H, W] / [9, P] ("planar").  lu, lv: scalars or
+    E directions.  Returns [E, H, W, 3], squeezed to [H, W, 3] for scalar directions, in out_dtype: float32,
+    or int32 / uint8 converted as ``relight`` does."""
+    _require_cuda(lrgb, "lrgb")
+    cl = _layout_id(layout)
+    spatial = _coef_spatial(lrgb, 9, cl)
+    if out_dtype not in _ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    scalar = np.ndim(lu) == 0 and np.ndim(lv) == 0
+    luv = np.stack([np.asarray(lu, np.float64).ravel(), np.asarray(lv, np.float64).ravel()], -1)
+    luv_d = torch.as_tensor(np.ascontiguousarray(luv), device=lrgb.device)
+    E = luv.shape[0]
+    out = torch.empty((E,) + spatial + (3,), dtype=out_dtype, device=lrgb.device)
+    relight_lrgb_into(lrgb.contiguous(), luv_d, out, layout=cl)
+    return out[0] if scalar else out
+
+
+def lrgb_luminance(lrgb, layout="planar"):
+    """The luminance planes [6, H, W] of a planar LRGB map [9, H, W]: a view of the same storage, no copy.  It
+    is a dense planar PTM-6 map: ``normals``, ``relight_enhanced`` and ``unsharp`` take it with
+    layout="planar" (and ``relight`` gives the grey image).  Pixel-major maps raise ValueError: their
+    luminance is a strided map, which those entries do not support (fit with lrgb_layout="planar")."""
+    if _layout_id(layout) != L.RTI_COEF_PLANAR:
+        raise ValueError("lrgb_luminance needs a planar LRGB map [9, ...]: the luminance of a pixel-major map is "
+                         "strided, which normals / relight_enhanced / unsharp do not take")
+    if not torch.is_tensor(lrgb) or lrgb.dim() < 2 or lrgb.shape[0] != 9 or not lrgb.is_contiguous():
+        raise ValueError(f"lrgb must be a contiguous planar LRGB map [9, ...]; got {tuple(getattr(lrgb, 'shape', ()))}")
+    return lrgb[:6]
+
+
 # ---- light operators (RBF, fused PTM/HSH fit + evaluation) ----------------------------------
 
 def _query(qu, qv):

@@ -102,3 +102,135 @@ def write_tables(tables, filename):
 def read_tables(filename):
     """Read the reference's relight tables back as an int32 ndarray [G, G, R, R]."""
     return np.asarray(read_from_file(filename, compressed=False), dtype=np.int32)
+
+
+# ---- .ptm files (PTM 1.2, the uncompressed LRGB and RGB payloads; layout restated in DESIGN.md §4.7) ----------
+#   header, ASCII tokens: PTM_1.2, PTM_FORMAT_LRGB | PTM_FORMAT_RGB, W, H, six scales, six biases
+#   payload, unsigned bytes, scanlines bottom row first; coefficient = (raw − bias_j)·scale_j
+#     LRGB: H·W·6 coefficient bytes (a0..a5 per pixel), then H·W·3 bytes R G B per pixel
+#     RGB:  three such coefficient blocks, R then G then B
+_PTM_MAGIC = b"PTM_1.2"
+_PTM_FORMATS = {b"PTM_FORMAT_LRGB": "lrgb", b"PTM_FORMAT_RGB": "rgb"}
+_PTM_NOT_BUILT = (b"PTM_FORMAT_LUM", b"PTM_FORMAT_JPEG_LRGB", b"PTM_FORMAT_JPEG_RGB")
+
+
+def _host_f64(maps):
+    """A map as a host fp64 array; CUDA (or any torch) tensors are brought to the host."""
+    if hasattr(maps, "detach"):
+        maps = maps.detach().cpu().numpy()
+    return np.asarray(maps, dtype=np.float64)
+
+
+def _ptm_quantise(v):
+    """v [..., 6] fp64 -> (raw uint8 [..., 6], scale fp64 [6], bias int [6]): per coefficient j over the finite
+    values, scale = (hi − lo)/255 (1 when hi = lo or nothing is finite), bias = clip(rint(−lo/scale), 0, 255),
+    raw = clip(rint(v/scale + bias), 0, 255); a NaN writes raw = bias."""
+    scale, bias = np.ones(6), np.zeros(6, np.int64)
+    raw = np.empty(v.shape, np.uint8)
+    for j in range(6):
+        x = v[..., j]
+        fin = x[np.isfinite(x)]
+        if fin.size and fin.max() > fin.min():
+            scale[j] = (fin.max() - fin.min()) / 255.0
+        if fin.size:
+            bias[j] = int(np.clip(np.rint(-fin.min() / scale[j]), 0, 255))
+        with np.errstate(invalid="ignore"):
+            q = np.clip(np.rint(x / scale[j] + bias[j]), 0, 255)
+        raw[..., j] = np.where(np.isnan(x), bias[j], q).astype(np.uint8)
+    return raw, scale, bias
+
+
+def write_ptm(path, maps, format="lrgb"):
+    """Write an uncompressed PTM 1.2 file.  format="lrgb": maps [H, W, 9] (``fit_lrgb``, pixel-major);
+    format="rgb": maps [3, H, W, 6] (``fit`` of a colour stack).  Arrays or tensors on any device.
+
+    Coefficients are quantised to bytes per coefficient plane (one scale and bias per coefficient, shared by the
+    three channels of an RGB file); a plane whose values do not straddle zero loses what lies above 255·scale,
+    because the format's bias is a byte.  LRGB colours are stored as bytes of chroma/s with s the largest finite
+    chroma, and the luminance is multiplied by s: the product chroma·L survives, the normalisation
+    Σ w·chroma = 1 does not.  Returns path."""
+    m = _host_f64(maps)
+    if format == "lrgb":
+        if m.ndim != 3 or m.shape[2] != 9:
+            raise ValueError(f"an LRGB map is [H, W, 9]; got {m.shape}")
+        H, W = m.shape[:2]
+        chroma = m[..., 6:]
+        fin = chroma[np.isfinite(chroma)]
+        s = float(fin.max()) if fin.size and fin.max() > 0 else 1.0
+        with np.errstate(invalid="ignore"):
+            rgb = np.clip(np.rint(255.0 * chroma / s), 0, 255)
+        rgb = np.where(np.isnan(chroma), 0, rgb).astype(np.uint8)
+        raw, scale, bias = _ptm_quantise(m[..., :6] * s)
+        blocks = [raw[::-1], rgb[::-1]]
+        tag = b"PTM_FORMAT_LRGB"
+    elif format == "rgb":
+        if m.ndim != 4 or m.shape[0] != 3 or m.shape[3] != 6:
+            raise ValueError(f"RGB coefficient maps are [3, H, W, 6]; got {m.shape}")
+        H, W = m.shape[1:3]
+        raw, scale, bias = _ptm_quantise(m)
+        blocks = [raw[c, ::-1] for c in range(3)]
+        tag = b"PTM_FORMAT_RGB"
+    else:
+        raise ValueError(f"unknown PTM format {format!r} (expected 'lrgb' or 'rgb')")
+    if H < 1 or W < 1:
+        raise ValueError(f"empty map {m.shape}")
+    head = b"\n".join([_PTM_MAGIC, tag, b"%d" % W, b"%d" % H, " ".join("%.9g" % x for x in scale).encode(),
+                       " ".join("%d" % b for b in bias).encode()]) + b"\n"
+    with open(path, "wb") as f:
+        f.write(head)
+        for b in blocks:
+            f.write(np.ascontiguousarray(b).tobytes())
+    return path
+
+
+def _ptm_tokens(buf, n):
+    """The first n whitespace-separated tokens of buf and the offset of the byte after the last one."""
+    toks, i = [], 0
+    while len(toks) < n:
+        while i < len(buf) and buf[i:i + 1].isspace():
+            i += 1
+        j = i
+        while j < len(buf) and not buf[j:j + 1].isspace():
+            j += 1
+        if j == i:
+            raise ValueError("PTM header ends early")
+        toks.append(buf[i:j])
+        i = j
+    return toks, i
+
+
+def read_ptm(path):
+    """Read an uncompressed PTM 1.2 file -> ``(format, maps)``: ("lrgb", fp32 [H, W, 9]) or ("rgb", fp32
+    [3, H, W, 6]), rows top first as ``write_ptm`` takes them.  Any whitespace may separate the header's tokens;
+    the payload starts one byte after the last bias.  LRGB chroma is byte/255.  The LUM and JPEG formats raise
+    NotImplementedError, a bad magic or a short payload ValueError."""
+    with open(path, "rb") as f:
+        buf = f.read()
+    (magic, tag), _ = _ptm_tokens(buf, 2)
+    if magic != _PTM_MAGIC:
+        raise ValueError(f"not a PTM 1.2 file: magic {magic[:16]!r}")
+    if tag in _PTM_NOT_BUILT:
+        raise NotImplementedError(f"{tag.decode()} files are not built (uncompressed LRGB and RGB only)")
+    if tag not in _PTM_FORMATS:
+        raise ValueError(f"unknown PTM format {tag[:32]!r}")
+    toks, end = _ptm_tokens(buf, 16)
+    try:
+        W, H = int(toks[2]), int(toks[3])
+        scale = np.array([float(t) for t in toks[4:10]])
+        bias = np.array([int(t) for t in toks[10:16]], np.float64)
+    except ValueError:
+        raise ValueError("malformed PTM header") from None
+    if W < 1 or H < 1:
+        raise ValueError(f"PTM header: bad size {W} x {H}")
+    fmt = _PTM_FORMATS[tag]
+    n = H * W
+    need = 9 * n if fmt == "lrgb" else 18 * n
+    data = np.frombuffer(buf, np.uint8, offset=min(end + 1, len(buf)))
+    if data.size < need:
+        raise ValueError(f"short PTM payload: {data.size} of {need} bytes")
+    if fmt == "lrgb":
+        coef = (data[:6 * n].reshape(H, W, 6)[::-1].astype(np.float64) - bias) * scale
+        rgb = data[6 * n:9 * n].reshape(H, W, 3)[::-1].astype(np.float64) / 255.0
+        return fmt, np.concatenate([coef, rgb], -1).astype(np.float32)
+    coef = (data[:18 * n].reshape(3, H, W, 6)[:, ::-1].astype(np.float64) - bias) * scale
+    return fmt, coef.astype(np.float32)

@@ -1,12 +1,14 @@
 """PyTorch custom ops over the C ABI: ``torch.ops.rti.fit_shared`` / ``fit_shared_residual`` /
 ``fit_robust`` / ``fit_accumulate`` / ``fit_accum_solve`` / ``fit_residual`` / ``relight`` / ``ptm_normals`` /
-``relight_enhanced`` / ``map_unsharp`` / ``shade_normals``.
+``relight_enhanced`` / ``map_unsharp`` / ``shade_normals`` / ``lrgb_from_rgb`` / ``relight_lrgb``.
 
 They let the fit and relight kernels sit inside torch programs (and
 ``torch.library`` fake-tensor tracing) while the compute stays in librti's
 HIP kernels on the current stream.
 """
 from __future__ import annotations
+
+from typing import Optional, Sequence
 
 import torch
 
@@ -330,3 +332,45 @@ def shade_normals(n: torch.Tensor, lu: float, lv: float, albedo: torch.Tensor | 
 @shade_normals.register_fake
 def _(n, lu, lv, albedo=None, kd=1.0, ks=0.0, exp=1, planar=False, out_dtype=torch.float32):
     return n.new_empty((n.shape[1 if planar else 0],), dtype=out_dtype)
+
+
+@torch.library.custom_op("rti::lrgb_from_rgb", mutates_args=())
+def lrgb_from_rgb(coef: torch.Tensor, gram: torch.Tensor, weights: Optional[Sequence[float]] = None,
+                  planar: bool = False, lrgb_planar: bool = False) -> torch.Tensor:
+    """Three PTM-6 maps -> one LRGB map (``rti_lrgb_from_rgb``).  coef CUDA fp32 [3, P, 6] (or [3, 6, P] if
+    planar), gram [6, 6] (``rti.gram``; read on the host), weights None (1/3 each) or 3 values -> fp32 [P, 9]
+    (or [9, P] if lrgb_planar)."""
+    api._require_cuda(coef, "coef")
+    if coef.dim() != 3 or coef.shape[0] != 3 or coef.shape[1 if planar else 2] != 6:
+        raise ValueError(f"coef must be {'[3, 6, P]' if planar else '[3, P, 6]'}; got {tuple(coef.shape)}")
+    P = coef.shape[2 if planar else 1]
+    out = coef.new_empty((9, P) if lrgb_planar else (P, 9), dtype=torch.float32)
+    return api.lrgb_from_rgb_into(coef.contiguous(), gram, out, weights=weights,
+                                  layout="planar" if planar else "pixel",
+                                  lrgb_layout="planar" if lrgb_planar else "pixel")
+
+
+@lrgb_from_rgb.register_fake
+def _(coef, gram, weights=None, planar=False, lrgb_planar=False):
+    P = coef.shape[2 if planar else 1]
+    return coef.new_empty((9, P) if lrgb_planar else (P, 9), dtype=torch.float32)
+
+
+@torch.library.custom_op("rti::relight_lrgb", mutates_args=())
+def relight_lrgb(lrgb: torch.Tensor, luv: torch.Tensor, planar: bool = False,
+                 out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """RGB images of an LRGB map (``rti_relight_lrgb``).  lrgb CUDA fp32 [P, 9] (or [9, P] if planar), luv
+    [E, 2] -> [E, P, 3] in out_dtype (float32, int32 or uint8)."""
+    api._require_cuda(lrgb, "lrgb")
+    if lrgb.dim() != 2 or lrgb.shape[0 if planar else 1] != 9:
+        raise ValueError(f"lrgb must be {'[9, P]' if planar else '[P, 9]'}; got {tuple(lrgb.shape)}")
+    if out_dtype not in api._ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    luv_d = luv.detach().to(device=lrgb.device, dtype=torch.float64).contiguous()
+    out = lrgb.new_empty((luv.shape[0], lrgb.shape[1 if planar else 0], 3), dtype=out_dtype)
+    return api.relight_lrgb_into(lrgb.contiguous(), luv_d, out, layout="planar" if planar else "pixel")
+
+
+@relight_lrgb.register_fake
+def _(lrgb, luv, planar=False, out_dtype=torch.float32):
+    return lrgb.new_empty((luv.shape[0], lrgb.shape[1 if planar else 0], 3), dtype=out_dtype)
