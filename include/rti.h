@@ -646,6 +646,47 @@ int rti_lrgb_from_rgb(const float* coef, int coef_layout, int64_t coef_channel_s
 int rti_relight_lrgb(const float* lrgb, int lrgb_layout, int64_t P, const double* luv, int E,
                      void* out, int out_dtype, rti_stream_t stream);
 
+/* ---- device: 8-bit LRGB PTMs, the .ptm payload (rti_lrgb8.hip) ----------------------------------
+ * A quantised LRGB map ("LRGB8") is the two blocks of a PTM_FORMAT_LRGB payload and its header values:
+ *   coef8:   uint8 [p][6], the bytes a0..a5 of every pixel;   rgb8: uint8 [p][3];
+ *   qparams: device fp64 [13]: scale[0..5], bias[0..5] (integral values), s (the chroma scale).
+ * Rows top first, as every map of the project (a file stores them bottom first: the flip is the host's).
+ * The arithmetic is that of rti/io.py (write_ptm, _ptm_quantise, read_ptm), in fp64
+ * from the fp32 map, no contraction, each expression left to right as written.
+ * rti_lrgb_qparams_workspace: bytes of device scratch rti_lrgb_qparams needs for P pixels (0 for P < 1);
+ *   monotone in P and at most 39936.
+ * rti_lrgb_qparams: lrgb: an fp32 LRGB map, [p][9] or [9][p] (lrgb_layout).  One pass finds, over the finite
+ *   values, cmax = the largest of the three chroma planes and lo_j, hi_j of luminance plane j; then
+ *     s       = cmax if there is a finite chroma value and cmax > 0, else 1
+ *     LO_j    = (double)lo_j·s, HI_j = (double)hi_j·s
+ *     scale_j = (HI_j − LO_j)/255.0 if plane j has a finite value and HI_j > LO_j, else 1
+ *     bias_j  = clip(rint(−LO_j/scale_j), 0, 255) if plane j has a finite value, else 0
+ *   (min and max are order-independent, so the result does not depend on the reduction tree; no atomics).
+ *   workspace: 4-byte aligned, need not be initialised: the entry reads only what it wrote.  Two launches.
+ *   36 bytes in per pixel.
+ * rti_lrgb_quantise: per pixel, x = (double)a_j·s, raw_j = clip(rint(x/scale_j + bias_j), 0, 255), a NaN a_j
+ *   writes bias_j, ±inf saturates; colour byte c = clip(rint(255.0·(double)chroma_c/s), 0, 255), a NaN writes
+ *   0.  36 bytes in and 9 out per pixel.
+ * rti_relight_lrgb8: reads scale and bias of qparams (not s).  Per pixel
+ *     a_j = (float)(((double)raw_j − bias_j)·scale_j),  chroma_c = (float)((double)byte_c/255.0)
+ *   -- the fp32 map read_ptm builds -- and then L, the three channels, their conversion and out[e][p][c] exactly
+ *   as rti_relight_lrgb, so the image equals rti_relight_lrgb's of that map bit for bit.  The 9 bytes are read
+ *   once for all E directions: 9 bytes in and 3·sizeof(out) per direction out per pixel.
+ * All: device pointers, stream-ordered, no allocation, no synchronisation, capturable in a hipGraph.  Every
+ * argument check answers before any HIP call.  RTI_ERR_BAD_ARG: a null pointer; P < 1 (or E < 1); a bad
+ * layout; a misaligned workspace (4) or qparams (8).  RTI_ERR_UNSUPPORTED: an out_dtype other than F32 / I32 /
+ * U8.  The vector path (one lane = 4 pixels, the byte blocks as whole dwords) needs P % 4 == 0, the fp32 map
+ * 16-byte aligned, coef8 4-byte (rti_relight_lrgb8: 8-byte) and rgb8 4-byte aligned, and out aligned as
+ * rti_relight_lrgb requires; anything else, and the last partial 256-pixel chunk, runs one pixel per lane with
+ * the same arithmetic and bits. */
+int64_t rti_lrgb_qparams_workspace(int64_t P);
+int rti_lrgb_qparams(const float* lrgb, int lrgb_layout, int64_t P, void* workspace, double* qparams,
+                     rti_stream_t stream);
+int rti_lrgb_quantise(const float* lrgb, int lrgb_layout, int64_t P, const double* qparams,
+                      uint8_t* coef8, uint8_t* rgb8, rti_stream_t stream);
+int rti_relight_lrgb8(const uint8_t* coef8, const uint8_t* rgb8, int64_t P, const double* qparams,
+                      const double* luv, int E, void* out, int out_dtype, rti_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

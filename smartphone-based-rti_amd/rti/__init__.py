@@ -20,6 +20,11 @@ bara96/Smartphone-based-RTI: analysis.py:196-411, interactive_relighting.py:11-3
     rgb = rti.relight_lrgb(m, 0.3, -0.2, out_dtype=torch.uint8)   # [H, W, 3] in one launch
     rti.write_ptm("object.ptm", m)                   # opens in a PTM viewer
 
+    q = rti.quantise_lrgb(m)                         # the file's 9 bytes per pixel, made on the GPU
+    rgb = rti.relight_lrgb8(q, 0.3, -0.2, out_dtype=torch.uint8)  # rendered from the bytes
+    rti.write_ptm("object.ptm", q)                   # the same file, without the fp32 copy to the host
+    q = rti.read_ptm("object.ptm", quantised=True)[1].to("cuda")  # a loaded file stays 9 bytes per pixel
+
 Compute runs in HIP kernels of librti.so (include/rti.h); importing this
 package does not touch the GPU.
 """
@@ -31,7 +36,9 @@ from .api import (BASES, FitAccumulator, apply_operator, basis_eval, basis_id, b
                   interpolate_rbf, interpolate_rbf_perpixel, light_dirs, lsq_factors, pinv, q8_operator, h16_operator, rbf_operator,
                   normals, ptm_normals_into, relight, relight_enhanced, relight_enhanced_into, relight_frame,
                   gauss_taps, map_unsharp_into, normals_unsharp, shade_normals, shade_normals_into, unsharp,
-                  fit_lrgb, gram, lrgb_from_rgb, lrgb_from_rgb_into, lrgb_luminance, relight_lrgb, relight_lrgb_into)
+                  fit_lrgb, gram, lrgb_from_rgb, lrgb_from_rgb_into, lrgb_luminance, relight_lrgb, relight_lrgb_into,
+                  QuantisedLRGB, dequantise_lrgb, lrgb_qparams_into, lrgb_qparams_workspace, lrgb_quantise_into,
+                  quantise_lrgb, relight_lrgb8, relight_lrgb8_into)
 from .io import read_ptm, write_ptm
 
 __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_into", "fit_chunked",
@@ -43,7 +50,9 @@ __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_in
            "rbf_operator", "relight", "relight_frame", "normals", "ptm_normals_into", "relight_enhanced",
            "relight_enhanced_into", "gauss_taps", "map_unsharp_into", "normals_unsharp", "shade_normals",
            "shade_normals_into", "unsharp", "fit_lrgb", "gram", "lrgb_from_rgb", "lrgb_from_rgb_into",
-           "lrgb_luminance", "relight_lrgb", "relight_lrgb_into", "read_ptm", "write_ptm", "library_path", "load"]
+           "lrgb_luminance", "relight_lrgb", "relight_lrgb_into", "QuantisedLRGB", "dequantise_lrgb",
+           "lrgb_qparams_into", "lrgb_qparams_workspace", "lrgb_quantise_into", "quantise_lrgb", "relight_lrgb8",
+           "relight_lrgb8_into", "read_ptm", "write_ptm", "library_path", "load"]
 
 __version__ = "0.1.0"
 

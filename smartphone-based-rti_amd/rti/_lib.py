@@ -163,6 +163,11 @@ SIGNATURES = {
     "rti_lrgb_from_rgb": (_c_int, [_c_void_p, _c_int, _c_i64, _c_i64, _c_double_p, _c_double_p, _c_void_p, _c_int,
                                    _c_void_p]),
     "rti_relight_lrgb": (_c_int, [_c_void_p, _c_int, _c_i64, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p]),
+    "rti_lrgb_qparams_workspace": (_c_i64, [_c_i64]),
+    "rti_lrgb_qparams": (_c_int, [_c_void_p, _c_int, _c_i64, _c_void_p, _c_void_p, _c_void_p]),
+    "rti_lrgb_quantise": (_c_int, [_c_void_p, _c_int, _c_i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "rti_relight_lrgb8": (_c_int, [_c_void_p, _c_void_p, _c_i64, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int,
+                                   _c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -1323,6 +1323,208 @@ def lrgb_luminance(lrgb, layout="planar"):
     return lrgb[:6]
 
 
+# ---- 8-bit LRGB PTMs: the .ptm payload on the device (rti_lrgb8.hip) ---------
+
+class QuantisedLRGB:
+    """An 8-bit LRGB PTM: the two blocks of a ``PTM_FORMAT_LRGB`` payload and its header values.
+
+    coef: uint8 [H, W, 6] or [P, 6], the bytes a0..a5 per pixel; rgb: uint8 [..., 3]; qparams: fp64 [13] =
+    scale[0..5], bias[0..5] (integral), s (the chroma scale the quantiser used; 1 for a map read from a file,
+    which does not carry it).  Rows top first.  All three tensors on one device (the GPU, or the host for
+    ``read_ptm(path, quantised=True)``); immutable.  ``scale`` / ``bias`` / ``s`` copy qparams to the host: they
+    are the one accessor that synchronises."""
+    __slots__ = ("_coef", "_rgb", "_qparams")
+
+    def __init__(self, coef, rgb, qparams):
+        if not (torch.is_tensor(coef) and torch.is_tensor(rgb) and torch.is_tensor(qparams)):
+            raise ValueError("QuantisedLRGB takes three tensors (coef, rgb, qparams)")
+        if coef.dtype != torch.uint8 or coef.dim() < 2 or coef.shape[-1] != 6 or coef.numel() == 0 \
+                or not coef.is_contiguous():
+            raise ValueError(f"coef must be a contiguous uint8 [..., 6] tensor; got {coef.dtype} {tuple(coef.shape)}")
+        if rgb.dtype != torch.uint8 or tuple(rgb.shape) != tuple(coef.shape[:-1]) + (3,) or not rgb.is_contiguous():
+            raise ValueError(f"rgb must be a contiguous uint8 {tuple(coef.shape[:-1]) + (3,)} tensor; got "
+                             f"{rgb.dtype} {tuple(rgb.shape)}")
+        if qparams.dtype != torch.float64 or tuple(qparams.shape) != (13,) or not qparams.is_contiguous():
+            raise ValueError(f"qparams must be a contiguous float64 [13] tensor; got {qparams.dtype} "
+                             f"{tuple(qparams.shape)}")
+        if not coef.device == rgb.device == qparams.device:
+            raise ValueError(f"coef, rgb and qparams must be on one device; got {coef.device}, {rgb.device}, "
+                             f"{qparams.device}")
+        for name, v in zip(self.__slots__, (coef, rgb, qparams)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("QuantisedLRGB is immutable")
+
+    coef = property(lambda self: self._coef)
+    rgb = property(lambda self: self._rgb)
+    qparams = property(lambda self: self._qparams)
+    shape = property(lambda self: tuple(self._coef.shape[:-1]), doc="the spatial shape: (H, W) or (P,)")
+    device = property(lambda self: self._coef.device)
+
+    def _host(self):
+        return self._qparams.detach().cpu().numpy()
+
+    scale = property(lambda self: self._host()[:6].copy(), doc="host fp64 [6] (synchronises)")
+    bias = property(lambda self: self._host()[6:12].copy(), doc="host fp64 [6], integral values (synchronises)")
+    s = property(lambda self: float(self._host()[12]), doc="the chroma scale, a host float (synchronises)")
+
+    def to(self, device):
+        return QuantisedLRGB(self._coef.to(device), self._rgb.to(device), self._qparams.to(device))
+
+    def with_file_scales(self):
+        """The map as a .ptm round trip yields it: the same bytes, the scales rounded to the nine significant
+        digits ``write_ptm`` puts in the header, s = 1.  ``quantise_lrgb`` keeps the full fp64 scales the bytes
+        were made with; a file does not, so ``dequantise_lrgb`` / ``relight_lrgb8`` of this map, not of the fresh
+        one, equal ``read_ptm`` of the written file to the bit.  Synchronises."""
+        qp = self._host().copy()
+        qp[:6] = [float("%.9g" % x) for x in qp[:6]]
+        qp[12] = 1.0
+        return QuantisedLRGB(self._coef, self._rgb, torch.as_tensor(qp).to(self.device))
+
+    def __repr__(self):
+        return f"QuantisedLRGB(shape={self.shape}, device={self.device})"
+
+
+def _quantised(q, name="q"):
+    """A QuantisedLRGB on the GPU -> P."""
+    if not isinstance(q, QuantisedLRGB):
+        raise ValueError(f"{name} must be a QuantisedLRGB (quantise_lrgb, or read_ptm(path, quantised=True)); got "
+                         f"{type(q).__name__}")
+    _require_cuda(q.coef, f"{name}.coef")
+    return q.coef.numel() // 6
+
+
+def _qparams_dev(qparams, like):
+    _require_cuda(qparams, "qparams")
+    if qparams.dtype != torch.float64 or qparams.numel() != 13 or not qparams.is_contiguous() \
+            or qparams.device != like.device:
+        raise ValueError(f"qparams must be a contiguous float64 [13] tensor on {like.device}; got {qparams.dtype} "
+                         f"{tuple(qparams.shape)} on {qparams.device}")
+    return _vp(qparams)
+
+
+def lrgb_qparams_workspace(P):
+    """Bytes of device scratch ``lrgb_qparams_into`` needs for P pixels (``rti_lrgb_qparams_workspace``)."""
+    n = int(L.lib().rti_lrgb_qparams_workspace(int(P)))
+    if n <= 0:
+        raise ValueError(f"P must be positive; got {P}")
+    return n
+
+
+def lrgb_qparams_into(lrgb, workspace, qparams, *, layout="pixel"):
+    """Launch ``rti_lrgb_qparams`` on preallocated tensors (no allocation, graph-capturable): the six scales, six
+    biases and the chroma scale ``write_ptm`` would give the map.
+
+    lrgb: contiguous CUDA fp32 [P, 9] (layout="pixel") or [9, P], any spatial shape in place of P; workspace: a
+    contiguous CUDA tensor of at least ``lrgb_qparams_workspace(P)`` bytes (it need not be initialised);
+    qparams: CUDA fp64 [13]."""
+    P = _lrgb_map(lrgb)
+    _require_cuda(workspace, "workspace")
+    need = lrgb_qparams_workspace(P)
+    if not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need \
+            or workspace.device != lrgb.device:
+        raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on {lrgb.device}; got "
+                         f"{workspace.numel() * workspace.element_size()} bytes on {workspace.device}")
+    st = L.lib().rti_lrgb_qparams(_vp(lrgb), _layout_id(layout), P, _vp(workspace), _qparams_dev(qparams, lrgb),
+                                  _stream_of(lrgb))
+    L.check(st, "rti_lrgb_qparams")
+    return qparams
+
+
+def lrgb_quantise_into(lrgb, qparams, coef8, rgb8, *, layout="pixel"):
+    """Launch ``rti_lrgb_quantise`` on preallocated tensors (no allocation, graph-capturable).
+
+    lrgb: as ``lrgb_qparams_into``; qparams: CUDA fp64 [13] (``lrgb_qparams_into``); coef8: uint8 with 6·P
+    elements ([P, 6]); rgb8: uint8 with 3·P elements ([P, 3]).  Returns (coef8, rgb8)."""
+    P = _lrgb_map(lrgb)
+    st = L.lib().rti_lrgb_quantise(_vp(lrgb), _layout_id(layout), P, _qparams_dev(qparams, lrgb),
+                                   _map_out(coef8, "coef8", torch.uint8, 6 * P, lrgb),
+                                   _map_out(rgb8, "rgb8", torch.uint8, 3 * P, lrgb), _stream_of(lrgb))
+    L.check(st, "rti_lrgb_quantise")
+    return coef8, rgb8
+
+
+def quantise_lrgb(lrgb, *, layout="pixel"):
+    """Quantise an LRGB map to the 9 bytes per pixel of a .ptm file on the GPU (``rti_lrgb_qparams`` then
+    ``rti_lrgb_quantise``): the bytes, scales and biases ``write_ptm`` computes on the host, without the copy.
+
+    lrgb: CUDA fp32 [H, W, 9] / [P, 9] (layout="pixel") or [9, H, W] / [9, P] ("planar").  Returns a
+    ``QuantisedLRGB`` on lrgb's device; ``write_ptm(path, q)`` writes it, ``relight_lrgb8`` renders it."""
+    _require_cuda(lrgb, "lrgb")
+    cl = _layout_id(layout)
+    spatial = _coef_spatial(lrgb, 9, cl)
+    m = lrgb.contiguous()
+    P = _lrgb_map(m)
+    ws = torch.empty(lrgb_qparams_workspace(P), dtype=torch.uint8, device=m.device)
+    qparams = torch.empty(13, dtype=torch.float64, device=m.device)
+    coef8 = torch.empty(spatial + (6,), dtype=torch.uint8, device=m.device)
+    rgb8 = torch.empty(spatial + (3,), dtype=torch.uint8, device=m.device)
+    lrgb_qparams_into(m, ws, qparams, layout=cl)
+    lrgb_quantise_into(m, qparams, coef8, rgb8, layout=cl)
+    return QuantisedLRGB(coef8, rgb8, qparams)
+
+
+def dequantise_lrgb(q):
+    """The fp32 LRGB map [..., 9] of a quantised one, with ``read_ptm``'s arithmetic: (byte − bias)·scale and
+    byte/255 in fp64, rounded once to fp32.  Plain torch operations on q's device (not a hot path): what
+    ``normals``, ``relight_enhanced`` and ``unsharp`` need to take a loaded file's luminance."""
+    if not isinstance(q, QuantisedLRGB):
+        raise ValueError(f"q must be a QuantisedLRGB; got {type(q).__name__}")
+    qp = q.qparams
+    coef = (q.coef.double() - qp[6:12]) * qp[:6]
+    # a tensor divisor: division by a Python scalar may be evaluated as a product with its reciprocal
+    rgb = q.rgb.double() / torch.full((1,), 255.0, dtype=torch.float64, device=q.device)
+    return torch.cat([coef, rgb], -1).float()
+
+
+def relight_lrgb8_into(coef8, rgb8, qparams, luv_dev, out):
+    """Launch ``rti_relight_lrgb8`` on preallocated tensors (no allocation, graph-capturable).
+
+    coef8: contiguous CUDA uint8 [P, 6], any spatial shape in place of P; rgb8: uint8 [P, 3]; qparams: CUDA fp64
+    [13]; luv_dev: CUDA fp64 [E, 2]; out: float32, int32 or uint8 with E·P·3 elements ([E, P, 3])."""
+    _require_cuda(coef8, "coef8")
+    if coef8.dtype != torch.uint8 or not coef8.is_contiguous() or coef8.numel() == 0 or coef8.numel() % 6:
+        raise ValueError(f"coef8 must be a contiguous uint8 map of 6 bytes per pixel; got {coef8.dtype} "
+                         f"{tuple(coef8.shape)}")
+    P = coef8.numel() // 6
+    _require_cuda(rgb8, "rgb8")
+    if rgb8.dtype != torch.uint8 or not rgb8.is_contiguous() or rgb8.numel() != 3 * P or rgb8.device != coef8.device:
+        raise ValueError(f"rgb8 must be a contiguous uint8 tensor of {3 * P} elements on {coef8.device}; got "
+                         f"{rgb8.dtype} {tuple(rgb8.shape)} on {rgb8.device}")
+    _require_cuda(luv_dev, "luv")
+    if luv_dev.dtype != torch.float64 or luv_dev.dim() != 2 or luv_dev.shape[1] != 2 or luv_dev.shape[0] < 1 \
+            or not luv_dev.is_contiguous() or luv_dev.device != coef8.device:
+        raise ValueError(f"luv must be a contiguous float64 [E, 2] tensor on {coef8.device}; got {luv_dev.dtype} "
+                         f"{tuple(luv_dev.shape)} on {luv_dev.device}")
+    E = luv_dev.shape[0]
+    odt = _ENHANCED_DTYPES.get(out.dtype) if torch.is_tensor(out) else None
+    if odt is None:
+        raise ValueError("out must be a float32, int32 or uint8 tensor")
+    st = L.lib().rti_relight_lrgb8(_vp(coef8), _vp(rgb8), P, _qparams_dev(qparams, coef8), _vp(luv_dev), E,
+                                   _map_out(out, "out", out.dtype, E * P * 3, coef8), odt, _stream_of(coef8))
+    L.check(st, "rti_relight_lrgb8")
+    return out
+
+
+def relight_lrgb8(q, lu, lv, *, out_dtype=torch.float32):
+    """Relight a quantised LRGB map to RGB images on the GPU in one launch (``rti_relight_lrgb8``), reading 9
+    bytes per pixel once for every direction.  The images equal ``relight_lrgb(dequantise_lrgb(q), lu, lv)``
+    bit for bit.
+
+    q: a ``QuantisedLRGB`` on the GPU.  lu, lv: scalars or E directions.  Returns [E, H, W, 3], squeezed to
+    [H, W, 3] for scalar directions, in out_dtype: float32, or int32 / uint8 converted as ``relight`` does."""
+    _quantised(q)
+    if out_dtype not in _ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    scalar = np.ndim(lu) == 0 and np.ndim(lv) == 0
+    luv = np.stack([np.asarray(lu, np.float64).ravel(), np.asarray(lv, np.float64).ravel()], -1)
+    luv_d = torch.as_tensor(np.ascontiguousarray(luv), device=q.device)
+    out = torch.empty((luv.shape[0],) + q.shape + (3,), dtype=out_dtype, device=q.device)
+    relight_lrgb8_into(q.coef, q.rgb, q.qparams, luv_d, out)
+    return out[0] if scalar else out
+
+
 # ---- light operators (RBF, fused PTM/HSH fit + evaluation) ----------------------------------
 
 def _query(qu, qv):

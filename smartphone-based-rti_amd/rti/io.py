@@ -148,7 +148,19 @@ def write_ptm(path, maps, format="lrgb"):
     three channels of an RGB file); a plane whose values do not straddle zero loses what lies above 255·scale,
     because the format's bias is a byte.  LRGB colours are stored as bytes of chroma/s with s the largest finite
     chroma, and the luminance is multiplied by s: the product chroma·L survives, the normalisation
-    Σ w·chroma = 1 does not.  Returns path."""
+    Σ w·chroma = 1 does not.  Returns path.
+
+    maps may also be a ``QuantisedLRGB`` [H, W] (``quantise_lrgb``, or ``read_ptm(path, quantised=True)``): its 9
+    bytes per pixel and 13 doubles are copied to the host and written as they are, with the same header."""
+    from .api import QuantisedLRGB
+
+    if isinstance(maps, QuantisedLRGB):
+        if format != "lrgb":
+            raise ValueError(f"a QuantisedLRGB is an LRGB payload; got format {format!r}")
+        if len(maps.shape) != 2:
+            raise ValueError(f"a file needs a map with rows: QuantisedLRGB [H, W]; got {maps.shape}")
+        raw, rgb = maps.coef.detach().cpu().numpy(), maps.rgb.detach().cpu().numpy()
+        return _ptm_write(path, b"PTM_FORMAT_LRGB", maps.shape, maps.scale, maps.bias, [raw[::-1], rgb[::-1]])
     m = _host_f64(maps)
     if format == "lrgb":
         if m.ndim != 3 or m.shape[2] != 9:
@@ -174,6 +186,12 @@ def write_ptm(path, maps, format="lrgb"):
         raise ValueError(f"unknown PTM format {format!r} (expected 'lrgb' or 'rgb')")
     if H < 1 or W < 1:
         raise ValueError(f"empty map {m.shape}")
+    return _ptm_write(path, tag, (H, W), scale, bias, blocks)
+
+
+def _ptm_write(path, tag, shape, scale, bias, blocks):
+    """The header (scales as %.9g, biases as integers) and the payload blocks, already bottom row first."""
+    H, W = shape
     head = b"\n".join([_PTM_MAGIC, tag, b"%d" % W, b"%d" % H, " ".join("%.9g" % x for x in scale).encode(),
                        " ".join("%d" % b for b in bias).encode()]) + b"\n"
     with open(path, "wb") as f:
@@ -199,11 +217,15 @@ def _ptm_tokens(buf, n):
     return toks, i
 
 
-def read_ptm(path):
+def read_ptm(path, quantised=False):
     """Read an uncompressed PTM 1.2 file -> ``(format, maps)``: ("lrgb", fp32 [H, W, 9]) or ("rgb", fp32
     [3, H, W, 6]), rows top first as ``write_ptm`` takes them.  Any whitespace may separate the header's tokens;
     the payload starts one byte after the last bias.  LRGB chroma is byte/255.  The LUM and JPEG formats raise
-    NotImplementedError, a bad magic or a short payload ValueError."""
+    NotImplementedError, a bad magic or a short payload ValueError.
+
+    quantised=True keeps an LRGB file's 9 bytes per pixel: ("lrgb", ``QuantisedLRGB`` [H, W]) of host tensors,
+    rows top first, the header's scales and biases and s = 1; ``.to(device)`` moves it to the GPU for
+    ``relight_lrgb8``.  RGB files raise NotImplementedError (quantised RGB maps are not built)."""
     with open(path, "rb") as f:
         buf = f.read()
     (magic, tag), _ = _ptm_tokens(buf, 2)
@@ -228,6 +250,16 @@ def read_ptm(path):
     data = np.frombuffer(buf, np.uint8, offset=min(end + 1, len(buf)))
     if data.size < need:
         raise ValueError(f"short PTM payload: {data.size} of {need} bytes")
+    if quantised:
+        if fmt != "lrgb":
+            raise NotImplementedError("read_ptm(quantised=True): quantised RGB (18-byte) maps are not built")
+        import torch
+
+        from .api import QuantisedLRGB
+
+        blocks = [data[a * n:b * n].reshape(H, W, b - a)[::-1].copy(order="C") for a, b in ((0, 6), (6, 9))]
+        qparams = np.concatenate([scale, bias, [1.0]])
+        return fmt, QuantisedLRGB(*(torch.from_numpy(x) for x in blocks + [qparams]))
     if fmt == "lrgb":
         coef = (data[:6 * n].reshape(H, W, 6)[::-1].astype(np.float64) - bias) * scale
         rgb = data[6 * n:9 * n].reshape(H, W, 3)[::-1].astype(np.float64) / 255.0

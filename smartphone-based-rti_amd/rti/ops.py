@@ -1,6 +1,7 @@
 """PyTorch custom ops over the C ABI: ``torch.ops.rti.fit_shared`` / ``fit_shared_residual`` /
 ``fit_robust`` / ``fit_accumulate`` / ``fit_accum_solve`` / ``fit_residual`` / ``relight`` / ``ptm_normals`` /
-``relight_enhanced`` / ``map_unsharp`` / ``shade_normals`` / ``lrgb_from_rgb`` / ``relight_lrgb``.
+``relight_enhanced`` / ``map_unsharp`` / ``shade_normals`` / ``lrgb_from_rgb`` / ``relight_lrgb`` /
+``lrgb_quantise`` / ``relight_lrgb8``.
 
 They let the fit and relight kernels sit inside torch programs (and
 ``torch.library`` fake-tensor tracing) while the compute stays in librti's
@@ -374,3 +375,48 @@ def relight_lrgb(lrgb: torch.Tensor, luv: torch.Tensor, planar: bool = False,
 @relight_lrgb.register_fake
 def _(lrgb, luv, planar=False, out_dtype=torch.float32):
     return lrgb.new_empty((luv.shape[0], lrgb.shape[1 if planar else 0], 3), dtype=out_dtype)
+
+
+@torch.library.custom_op("rti::lrgb_quantise", mutates_args=())
+def lrgb_quantise(lrgb: torch.Tensor, planar: bool = False) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """An LRGB map -> its .ptm bytes and header values (``rti_lrgb_qparams`` then ``rti_lrgb_quantise``).  lrgb
+    CUDA fp32 [P, 9] (or [9, P] if planar) -> (coef8 uint8 [P, 6], rgb8 uint8 [P, 3], qparams fp64 [13])."""
+    api._require_cuda(lrgb, "lrgb")
+    if lrgb.dim() != 2 or lrgb.shape[0 if planar else 1] != 9:
+        raise ValueError(f"lrgb must be {'[9, P]' if planar else '[P, 9]'}; got {tuple(lrgb.shape)}")
+    P = lrgb.shape[1 if planar else 0]
+    layout = "planar" if planar else "pixel"
+    m = lrgb.contiguous()
+    ws = lrgb.new_empty((api.lrgb_qparams_workspace(P),), dtype=torch.uint8)
+    qparams = lrgb.new_empty((13,), dtype=torch.float64)
+    coef8, rgb8 = lrgb.new_empty((P, 6), dtype=torch.uint8), lrgb.new_empty((P, 3), dtype=torch.uint8)
+    api.lrgb_qparams_into(m, ws, qparams, layout=layout)
+    api.lrgb_quantise_into(m, qparams, coef8, rgb8, layout=layout)
+    return coef8, rgb8, qparams
+
+
+@lrgb_quantise.register_fake
+def _(lrgb, planar=False):
+    P = lrgb.shape[1 if planar else 0]
+    return (lrgb.new_empty((P, 6), dtype=torch.uint8), lrgb.new_empty((P, 3), dtype=torch.uint8),
+            lrgb.new_empty((13,), dtype=torch.float64))
+
+
+@torch.library.custom_op("rti::relight_lrgb8", mutates_args=())
+def relight_lrgb8(coef8: torch.Tensor, rgb8: torch.Tensor, qparams: torch.Tensor, luv: torch.Tensor,
+                  out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """RGB images of a quantised LRGB map (``rti_relight_lrgb8``).  coef8 CUDA uint8 [P, 6], rgb8 uint8 [P, 3],
+    qparams fp64 [13], luv [E, 2] -> [E, P, 3] in out_dtype (float32, int32 or uint8)."""
+    api._require_cuda(coef8, "coef8")
+    if coef8.dim() != 2 or coef8.shape[1] != 6 or rgb8.dim() != 2 or tuple(rgb8.shape) != (coef8.shape[0], 3):
+        raise ValueError(f"coef8 must be [P, 6] and rgb8 [P, 3]; got {tuple(coef8.shape)} and {tuple(rgb8.shape)}")
+    if out_dtype not in api._ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    luv_d = luv.detach().to(device=coef8.device, dtype=torch.float64).contiguous()
+    out = coef8.new_empty((luv.shape[0], coef8.shape[0], 3), dtype=out_dtype)
+    return api.relight_lrgb8_into(coef8.contiguous(), rgb8.contiguous(), qparams.contiguous(), luv_d, out)
+
+
+@relight_lrgb8.register_fake
+def _(coef8, rgb8, qparams, luv, out_dtype=torch.float32):
+    return coef8.new_empty((luv.shape[0], coef8.shape[0], 3), dtype=out_dtype)
