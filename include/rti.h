@@ -687,6 +687,56 @@ int rti_lrgb_quantise(const float* lrgb, int lrgb_layout, int64_t P, const doubl
 int rti_relight_lrgb8(const uint8_t* coef8, const uint8_t* rgb8, int64_t P, const double* qparams,
                       const double* luv, int E, void* out, int out_dtype, rti_stream_t stream);
 
+/* ---- device: 8-bit RGB HSH maps, the .rti payload (rti_hsh8.hip) ---------------------------------
+ * A quantised RGB HSH map ("HSH8") is the payload of an HSH .rti file and its header values:
+ *   coef8:   uint8 [p][3][k]: pixel, then channel (R, G, B), then term;
+ *   qparams: device fp32 [2k]: scale[0..k-1], then bias[0..k-1], shared by the three channels and equal to
+ *            the file header's values bit for bit.
+ * k = 9 (RTI_BASIS_HSH9) or 16 (RTI_BASIS_HSH16); term j is column j of rti_basis_eval.  Rows top first, as
+ * every map of the project.  The arithmetic is build-defined.  Every operation below is
+ * rounded, nothing is contracted, each expression is evaluated left to right as written:
+ *   step_j = scale_j / 255.0f               one correctly rounded fp32 division per term, formed once per
+ *                                           workgroup, never per pixel
+ *   c_j    = (float)raw_j * step_j + bias_j  the fp32 map read_rti builds: a byte -> fp32 conversion, an fp32
+ *                                           multiply and an fp32 add, no FMA
+ * rti_hsh_qparams_workspace: bytes of device scratch rti_hsh_qparams needs for k terms and P pixels; 0 for
+ *   P < 1 or a k other than 9 / 16; monotone in P and at most 768·2k·4 (98304 for k = 16).
+ * rti_hsh_qparams: coef: device fp32, three HSH maps as rti_fit_shared writes them with C = 3: [c][p][k]
+ *   (RTI_COEF_PIXEL_MAJOR) or [c][k][p] (RTI_COEF_PLANAR), coef_channel_stride in elements, 0 = dense = k·P.
+ *   One pass finds lo_j and hi_j, the smallest and largest finite value of term j in the three channels
+ *   (exact fp32 values; min and max are order-independent, so the result does not depend on the reduction
+ *   tree; no atomics); then
+ *     bias_j  = lo_j (a zero of either sign is written as +0) if term j has a finite value, else 0
+ *     scale_j = hi_j − lo_j in fp32 if term j has a finite value and that difference is finite and > 0, else 1
+ *   workspace: 4-byte aligned, need not be initialised: the entry reads only what it wrote.  Two launches.
+ *   12k bytes in per pixel.
+ * rti_hsh_quantise: raw = clip(rint(((double)x − (double)bias_j) / (double)step_j), 0, 255); a NaN writes 0,
+ *   ±inf saturates.  fp64: the quantiser runs once per object.  12k bytes in and 3k out per pixel.
+ * rti_relight_hsh8: per pixel, channel and direction, rti_relight's F32 path applied to c_0..c_{k-1}: the
+ *   same basis_eval<float> of ((float)lu, (float)lv), the same chain of k fused multiply-adds, converted once
+ *   (F32; I32 / U8 as rti_relight).  out[e][p][c], RGB interleaved like rti_relight_lrgb's.  The image equals
+ *   rti_relight's of the dequantised map of channel c bit for bit.  The bytes are read once for all E
+ *   directions of a launch: 3k bytes in and 3·sizeof(out) per direction out per pixel.
+ * All: device pointers, stream-ordered, no allocation, no synchronisation, capturable in a hipGraph.  Every
+ * argument check answers before any HIP call.  RTI_ERR_BAD_ARG: a null pointer; P < 1 (or E < 1); a bad
+ * layout; a channel stride below dense; a misaligned workspace or qparams (4 bytes).  RTI_ERR_UNSUPPORTED: a
+ * basis other than HSH-9 / HSH-16; an out_dtype other than F32 / I32 / U8.
+ * Every kernel runs one pixel per lane, 64 consecutive pixels per wave.  The fast paths move a full wave's
+ * contiguous run as whole 16-byte (output images: 4-byte) pieces through LDS and need:
+ *   the fp32 maps, pixel-major:  coef 16-byte aligned and a channel stride that is a multiple of 4
+ *                                (planar maps are read per lane, coalesced as they are);
+ *   coef8 (read or written):     16-byte aligned;
+ *   out:                         4-byte aligned, and for U8 also P % 4 == 0.
+ * Anything else, and the last partial wave of any launch, loads and stores per lane through the same
+ * per-pixel arithmetic and gives the same bits. */
+int64_t rti_hsh_qparams_workspace(int k, int64_t P);
+int rti_hsh_qparams(const float* coef, int basis, int coef_layout, int64_t coef_channel_stride, int64_t P,
+                    void* workspace, float* qparams, rti_stream_t stream);
+int rti_hsh_quantise(const float* coef, int basis, int coef_layout, int64_t coef_channel_stride, int64_t P,
+                     const float* qparams, uint8_t* coef8, rti_stream_t stream);
+int rti_relight_hsh8(const uint8_t* coef8, int basis, int64_t P, const float* qparams,
+                     const double* luv, int E, void* out, int out_dtype, rti_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,551 @@
+// rti_hsh8.hip -- 8-bit RGB HSH maps (gfx950): the payload of an .rti file on the device.
+//
+//     rti_hsh_qparams    one pass over three fp32 HSH maps -> the file's k scales and k biases
+//     rti_hsh_quantise   the maps + those 2k floats -> 3k bytes per pixel, [p][c][k]
+//     rti_relight_hsh8   the bytes + scales and biases -> E interleaved RGB images
+//
+// The arithmetic is include/rti.h's: step_j = scale_j / 255.0f once per workgroup, a coefficient is
+// (float)raw·step_j + bias_j in two rounded fp32 operations, and an image is rti_relight's F32 path of those
+// coefficients (the same basis_eval<float>, the same FMA chain, cvt_out), so it equals rti_relight's of the map
+// read_rti builds bit for bit.  Only the quantiser uses fp64; nothing per pixel divides.
+//
+// Lane map: one pixel per lane, a wave owns 64 consecutive pixels, a workgroup 256.  A wave's bytes are one
+// contiguous run of 64·3k bytes (1728 or 3072) that starts on a 16-byte boundary whenever coef8 does, so a full
+// wave moves it as whole 16-byte pieces through its LDS slab (rti_relight.hip's load_coef_staged, for rows that
+// are not dword-aligned): a lane then takes its 3k bytes out of the slab as dwords, realigned with a funnel
+// shift for k = 9.  fp32 rows of the pixel-major maps and the output rows go through the slab the same way.
+// Anything the pieces cannot serve (a pointer off its alignment, the last partial wave) loads and stores per
+// lane, through the same per-pixel functions.
+//
+// The extremes are order-independent (min and max of finite values; a zero minimum is stored as +0), so the
+// reduction tree does not show in the result: a lane folds its pixels into 2k floats, a wave folds its lanes with
+// shuffles, a workgroup its waves through LDS, and every workgroup writes its 2k partials to the workspace; a
+// one-workgroup tail folds those.  No atomics, and no workspace word is read that this call did not write.
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+
+#include "rti_basis.h"
+#include "rti_convert.h"
+#include "rti_lrgb_px.h"
+#include "rti_stack.h"
+
+namespace rti {
+namespace {
+
+using lrgb_px::wave_lds_sync;
+
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int ECH = 64;             // directions per basis table in LDS (rti_relight's)
+constexpr int QP_MAX_BLOCKS = 768;  // the extremes' grid: 3 workgroups per CU of 256, each striding over chunks
+constexpr int CHUNK = 256;          // pixels of a workgroup
+
+inline int64_t qparams_blocks(int64_t P) {
+  const int64_t chunks = (P + CHUNK - 1) / CHUNK;
+  return chunks < QP_MAX_BLOCKS ? chunks : QP_MAX_BLOCKS;
+}
+
+// rti_relight.hip's dot_k for fp32: fused multiply-adds in term order.  A copy, as rti_lrgb_px.h's loads are:
+// bench.py hashes rti_relight.hip to decide whether profiles/traffic.json is stale.
+template <int K>
+__device__ __forceinline__ float dot_k(const float (&c)[K], const float* b) {
+  float acc = c[0] * b[0];
+#pragma unroll
+  for (int k = 1; k < K; ++k) acc = fmaf(c[k], b[k], acc);
+  return acc;
+}
+
+// ---- a wave's run of 64 rows of ROWB bytes through its slab ---------------------------------------------------
+// 64·ROWB is a multiple of 16 for every ROWB; the run's base must be 16-byte aligned.  The slab is only ever
+// accessed as uint32_t / u32x4 / bytes, with a wave-level release / acquire between its phases.
+
+template <int ROWB>
+constexpr int run_v4() { return 64 * ROWB / 16; }
+// + one piece: k = 9's realigning read (lane_words) takes one dword past the run
+constexpr int slab_v4(int a, int b) { return (a > b ? a : b) + 1; }
+
+template <int ROWB>
+__device__ __forceinline__ void run_in(const void* __restrict__ g, int lane, u32x4* __restrict__ slab) {
+  constexpr int NV = run_v4<ROWB>(), PIECES = (NV + 63) / 64;
+  const u32x4* g4 = static_cast<const u32x4*>(g);
+  u32x4 t[PIECES];
+#pragma unroll
+  for (int j = 0; j < PIECES; ++j)
+    if (j * 64 + lane < NV) t[j] = __builtin_nontemporal_load(g4 + j * 64 + lane);
+#pragma unroll
+  for (int j = 0; j < PIECES; ++j)
+    if (j * 64 + lane < NV) slab[j * 64 + lane] = t[j];
+  wave_lds_sync();
+}
+
+template <int ROWB>
+__device__ __forceinline__ void run_out(void* __restrict__ g, int lane, const u32x4* __restrict__ slab) {
+  constexpr int NV = run_v4<ROWB>(), PIECES = (NV + 63) / 64;
+  wave_lds_sync();
+  u32x4* g4 = static_cast<u32x4*>(g);
+#pragma unroll
+  for (int j = 0; j < PIECES; ++j)
+    if (j * 64 + lane < NV) g4[j * 64 + lane] = slab[j * 64 + lane];
+  wave_lds_sync();  // the slab may be written again
+}
+
+// the lane's row of NB bytes out of the slab as (NB + 3) / 4 dwords, byte i of the row in byte i % 4 of word i / 4
+template <int NB>
+__device__ __forceinline__ void lane_words(const u32x4* __restrict__ slab, int lane, uint32_t (&w)[(NB + 3) / 4]) {
+  constexpr int NW = (NB + 3) / 4;
+  if constexpr (NB % 16 == 0) {
+#pragma unroll
+    for (int j = 0; j < NB / 16; ++j) {
+      const u32x4 t = slab[lane * (NB / 16) + j];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) w[4 * j + i] = t[i];
+    }
+  } else {
+    const uint32_t* s = reinterpret_cast<const uint32_t*>(slab);
+    const int o = NB * lane, d0 = o >> 2, sh = 8 * (o & 3);
+    uint32_t d[NW + 1];
+#pragma unroll
+    for (int i = 0; i <= NW; ++i) d[i] = s[d0 + i];
+#pragma unroll
+    for (int i = 0; i < NW; ++i) w[i] = (uint32_t)((((uint64_t)d[i + 1] << 32) | d[i]) >> sh);
+  }
+  wave_lds_sync();  // every lane has its row: the slab may be written again
+}
+
+// the lane's row of NB bytes (packed as lane_words returns them) into the slab
+template <int NB>
+__device__ __forceinline__ void put_lane_words(u32x4* __restrict__ slab, int lane, const uint32_t (&w)[(NB + 3) / 4]) {
+  if constexpr (NB % 16 == 0) {
+#pragma unroll
+    for (int j = 0; j < NB / 16; ++j) {
+      u32x4 t;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) t[i] = w[4 * j + i];
+      slab[lane * (NB / 16) + j] = t;
+    }
+  } else {
+    uint8_t* s = reinterpret_cast<uint8_t*>(slab) + NB * lane;
+#pragma unroll
+    for (int i = 0; i < NB; ++i) s[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+  }
+}
+
+// ---- the three fp32 maps of a pixel -----------------------------------------------------------------------------
+// x[c][j] of pixel wave_px + lane.  staged (wave-uniform; pixel-major, a full wave, 16-byte aligned rows): the
+// wave's 64 rows of a channel are one run.  Otherwise a live lane loads its own values (planar maps: coalesced
+// as they are) and a lane past the image gets NaNs, which the extremes skip.
+template <int K, int CL>
+__device__ __forceinline__ void load_px(const float* __restrict__ coef, int64_t cs, int64_t P, int64_t wave_px, int lane,
+                                        bool live, bool staged, u32x4* __restrict__ slab, float (&x)[3][K]) {
+  if constexpr (CL == RTI_COEF_PIXEL_MAJOR) {
+    if (staged) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        run_in<4 * K>(coef + c * cs + wave_px * K, lane, slab);
+        uint32_t w[K];
+        lane_words<4 * K>(slab, lane, w);
+#pragma unroll
+        for (int j = 0; j < K; ++j) x[c][j] = __uint_as_float(w[j]);
+      }
+      return;
+    }
+  }
+  const int64_t p = wave_px + lane;
+#pragma unroll
+  for (int c = 0; c < 3; ++c)
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+      x[c][j] = !live ? NAN : CL == RTI_COEF_PLANAR ? coef[c * cs + (int64_t)j * P + p] : coef[c * cs + p * K + j];
+}
+
+// ---- extremes ----------------------------------------------------------------------------------------------------
+// q[j], q[K + j]: min and max of the finite values of term j in the three channels.  A term without a finite
+// value keeps lo = +inf > hi = -inf.
+
+template <int K>
+__device__ __forceinline__ float ext_fold(int i, float a, float b) { return i < K ? fminf(a, b) : fmaxf(a, b); }
+
+template <int K>
+__device__ __forceinline__ void ext_init(float (&q)[2 * K]) {
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    q[j] = INFINITY;
+    q[K + j] = -INFINITY;
+  }
+}
+
+// the workgroup's 256 lanes -> thread i < 2K returns value i
+template <int K>
+__device__ __forceinline__ float ext_block_fold(float (&q)[2 * K], float (*part)[2 * K]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < 2 * K; ++i) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) q[i] = ext_fold<K>(i, q[i], __shfl_xor(q[i], m, 64));
+    if (lane == 0) part[wave][i] = q[i];
+  }
+  __syncthreads();
+  const int i = threadIdx.x < 2 * K ? threadIdx.x : 0;
+  return ext_fold<K>(i, ext_fold<K>(i, part[0][i], part[1][i]), ext_fold<K>(i, part[2][i], part[3][i]));
+}
+
+template <int K, int CL>
+__global__ void __launch_bounds__(256)
+hsh_extremes_k(const float* __restrict__ coef, int64_t cs, int64_t P, int vin, float* __restrict__ partial) {
+  constexpr int SLAB = slab_v4(CL == RTI_COEF_PIXEL_MAJOR ? run_v4<4 * K>() : 0, 0);
+  __shared__ u32x4 slabs[4 * SLAB];
+  __shared__ float part[4][2 * K];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float q[2 * K];
+  ext_init<K>(q);
+  const int64_t chunks = (P + CHUNK - 1) / CHUNK;
+  for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
+    const int64_t wave_px = (c * 4 + wave) * 64;
+    if (wave_px >= P) continue;  // wave-uniform
+    float x[3][K];
+    load_px<K, CL>(coef, cs, P, wave_px, lane, wave_px + lane < P, vin && wave_px + 64 <= P, slabs + wave * SLAB, x);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch)
+#pragma unroll
+      for (int j = 0; j < K; ++j)
+        if (fabsf(x[ch][j]) <= FLT_MAX) {  // false for NaN
+          q[j] = fminf(q[j], x[ch][j]);
+          q[K + j] = fmaxf(q[K + j], x[ch][j]);
+        }
+  }
+  const float r = ext_block_fold<K>(q, part);
+  if (threadIdx.x < 2 * K) partial[(int64_t)blockIdx.x * (2 * K) + threadIdx.x] = r;
+}
+
+// n partials -> qparams; one workgroup
+template <int K>
+__global__ void __launch_bounds__(256)
+hsh_qparams_k(const float* __restrict__ partial, int n, float* __restrict__ qparams) {
+#pragma clang fp contract(off)
+  __shared__ float part[4][2 * K];
+  __shared__ float fin[2 * K];
+  float q[2 * K];
+  ext_init<K>(q);
+  for (int b = threadIdx.x; b < n; b += 256)
+#pragma unroll
+    for (int i = 0; i < 2 * K; ++i) q[i] = ext_fold<K>(i, q[i], partial[(int64_t)b * (2 * K) + i]);
+  const float r = ext_block_fold<K>(q, part);
+  if (threadIdx.x < 2 * K) fin[threadIdx.x] = r;
+  __syncthreads();
+  if (threadIdx.x < K) {
+    const int j = threadIdx.x;
+    const float lo = fin[j], hi = fin[K + j];
+    const bool has = lo <= hi;  // the term has a finite value
+    const float d = hi - lo;
+    qparams[j] = has && d > 0.0f && d <= FLT_MAX ? d : 1.0f;
+    qparams[K + j] = has ? lo + 0.0f : 0.0f;  // -0.0 -> +0.0: min(-0, +0) depends on the order
+  }
+}
+
+// ---- per-pixel quantisation and dequantisation ------------------------------------------------------------------
+
+// step[0..K-1] = scale_j / 255.0f (one correctly rounded fp32 division per term and workgroup), bias[0..K-1];
+// the caller synchronises the workgroup
+template <int K>
+__device__ __forceinline__ void load_steps(const float* __restrict__ qparams, float* __restrict__ qs) {
+#pragma clang fp contract(off)
+  if (threadIdx.x < K) {
+    qs[threadIdx.x] = qparams[threadIdx.x] / 255.0f;
+    qs[K + threadIdx.x] = qparams[K + threadIdx.x];
+  }
+}
+
+// rint(t) clipped to a byte; NaN -> 0
+__device__ __forceinline__ uint32_t byte_of(double t) {
+  const double r = rint(t);
+  return (uint32_t)(int)(r > 0.0 ? (r < 255.0 ? r : 255.0) : 0.0);
+}
+
+// three fp32 maps of a pixel -> its 3K bytes, [c][j], packed as lane_words packs them
+template <int K>
+__device__ __forceinline__ void quantise_px(const float (&x)[3][K], const float* __restrict__ qs,
+                                            uint32_t (&w)[(3 * K + 3) / 4]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int i = 0; i < (3 * K + 3) / 4; ++i) w[i] = 0;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const double step = (double)qs[j], bias = (double)qs[K + j];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int i = c * K + j;
+      w[i >> 2] |= byte_of(((double)x[c][j] - bias) / step) << (8 * (i & 3));
+    }
+  }
+}
+
+// 3K bytes -> the fp32 coefficients read_rti builds from them: a multiply and an add, each rounded
+template <int K>
+__device__ __forceinline__ void dequantise_px(const uint32_t (&w)[(3 * K + 3) / 4], const float* __restrict__ qs,
+                                              float (&c)[3][K]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const float step = qs[j], bias = qs[K + j];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      const int i = ch * K + j;
+      const float raw = (float)((w[i >> 2] >> (8 * (i & 3))) & 0xffu);
+      const float t = raw * step;
+      c[ch][j] = t + bias;
+    }
+  }
+}
+
+// ---- kernels ------------------------------------------------------------------------------------------------------
+// Both: wave w of workgroup g owns pixels [(4g + w)·64, + 64).
+
+template <int K, int CL>
+__global__ void __launch_bounds__(256)
+hsh_quantise_k(const float* __restrict__ coef, int64_t cs, int64_t P, int vin, int vout,
+               const float* __restrict__ qparams, uint8_t* __restrict__ coef8) {
+  constexpr int NB = 3 * K, NW = (NB + 3) / 4;
+  constexpr int SLAB = slab_v4(CL == RTI_COEF_PIXEL_MAJOR ? run_v4<4 * K>() : 0, run_v4<NB>());
+  __shared__ u32x4 slabs[4 * SLAB];
+  __shared__ float qs[2 * K];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  u32x4* slab = slabs + wave * SLAB;
+  load_steps<K>(qparams, qs);
+  __syncthreads();
+  const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 64;
+  if (wave_px >= P) return;  // wave-uniform; no workgroup barrier below
+  const int64_t p = wave_px + lane;
+  const bool live = p < P, full = wave_px + 64 <= P;
+  float x[3][K];
+  load_px<K, CL>(coef, cs, P, wave_px, lane, live, vin && full, slab, x);
+  uint32_t w[NW];
+  quantise_px<K>(x, qs, w);
+  if (vout && full) {  // wave-uniform
+    put_lane_words<NB>(slab, lane, w);
+    run_out<NB>(coef8 + wave_px * NB, lane, slab);
+  } else if (live) {
+#pragma unroll
+    for (int i = 0; i < NB; ++i) coef8[p * NB + i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
+  }
+}
+
+template <int K, typename TO>
+__global__ void __launch_bounds__(256)
+relight_hsh8_k(const uint8_t* __restrict__ coef8, int64_t P, int vin, int vout,
+               const float* __restrict__ qparams, const double* __restrict__ luv, int E, TO* __restrict__ out) {
+  constexpr int NB = 3 * K, NW = (NB + 3) / 4;
+  constexpr int SLAB = slab_v4(run_v4<NB>(), run_v4<12>());  // bytes in; 64 rows of 3 elements of <= 4 bytes out
+  __shared__ u32x4 slabs[4 * SLAB];
+  __shared__ float btab[ECH * K];
+  __shared__ float qs[2 * K];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  u32x4* slab = slabs + wave * SLAB;
+  load_steps<K>(qparams, qs);
+  __syncthreads();
+  // every lane stays to the end: the basis tables are filled by the whole workgroup
+  const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 64;
+  const int64_t p = wave_px + lane;
+  const bool live = p < P, full = wave_px + 64 <= P;  // full: wave-uniform
+  uint32_t w[NW];
+#pragma unroll
+  for (int i = 0; i < NW; ++i) w[i] = 0;
+  if (vin && full) {
+    run_in<NB>(coef8 + wave_px * NB, lane, slab);
+    lane_words<NB>(slab, lane, w);
+  } else if (live) {
+#pragma unroll
+    for (int i = 0; i < NB; ++i) w[i >> 2] |= (uint32_t)coef8[p * NB + i] << (8 * (i & 3));
+  }
+  float c[3][K];
+  dequantise_px<K>(w, qs, c);
+
+  for (int e0 = 0; e0 < E; e0 += ECH) {
+    const int ne = min(ECH, E - e0);
+    if (e0) __syncthreads();  // the previous table has been read
+    for (int i = threadIdx.x; i < ne; i += 256) {
+      float b[K];
+      hsh_eval<float>((float)luv[2 * (e0 + i)], (float)luv[2 * (e0 + i) + 1], K, b);  // basis_eval<float>'s HSH branch
+#pragma unroll
+      for (int k = 0; k < K; ++k) btab[i * K + k] = b[k];
+    }
+    __syncthreads();
+    for (int e = 0; e < ne; ++e) {
+      const float* b = btab + e * K;
+      TO o[3];
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) o[ch] = cvt_out<TO>(dot_k<K>(c[ch], b));
+      TO* rows = out + ((int64_t)(e0 + e) * P + wave_px) * 3;
+      if (vout && full) {  // wave-uniform: the wave's 192 elements as whole dwords
+        uint32_t* d = reinterpret_cast<uint32_t*>(rows);
+        const uint32_t* s = reinterpret_cast<const uint32_t*>(slab);
+        if constexpr (sizeof(TO) == 4) {
+          uint32_t* sw = reinterpret_cast<uint32_t*>(slab) + 3 * lane;
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) sw[ch] = __builtin_bit_cast(uint32_t, o[ch]);
+          wave_lds_sync();
+#pragma unroll
+          for (int j = 0; j < 3; ++j) d[j * 64 + lane] = s[j * 64 + lane];
+        } else {
+          uint8_t* sb = reinterpret_cast<uint8_t*>(slab) + 3 * lane;
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) sb[ch] = o[ch];
+          wave_lds_sync();
+          if (lane < 48) d[lane] = s[lane];
+        }
+        wave_lds_sync();  // the slab may be written again
+      } else if (live) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) rows[3 * lane + ch] = o[ch];
+      }
+    }
+  }
+}
+
+struct HshArgs {
+  const float* coef;
+  int layout;
+  int64_t cs, P;
+  int vin;
+  hipStream_t s;
+};
+
+template <int K, int CL>
+void launch_extremes(const HshArgs& a, int blocks, float* partial) {
+  hipLaunchKernelGGL((hsh_extremes_k<K, CL>), dim3(blocks), dim3(256), 0, a.s, a.coef, a.cs, a.P, a.vin, partial);
+}
+
+template <int K, int CL>
+void launch_quantise(const HshArgs& a, int vout, const float* qparams, uint8_t* coef8) {
+  hipLaunchKernelGGL((hsh_quantise_k<K, CL>), dim3(grid_1d(a.P, CHUNK)), dim3(256), 0, a.s, a.coef, a.cs, a.P, a.vin,
+                     vout, qparams, coef8);
+}
+
+// f.template operator()<K, CL>() for the call's term count and layout
+template <typename F>
+void with_k_layout(int k, int layout, F&& f) {
+  if (k == 9) {
+    if (layout == RTI_COEF_PLANAR) f.template operator()<9, RTI_COEF_PLANAR>();
+    else f.template operator()<9, RTI_COEF_PIXEL_MAJOR>();
+  } else {
+    if (layout == RTI_COEF_PLANAR) f.template operator()<16, RTI_COEF_PLANAR>();
+    else f.template operator()<16, RTI_COEF_PIXEL_MAJOR>();
+  }
+}
+
+struct Extremes {
+  const HshArgs& a;
+  int blocks;
+  float* partial;
+  template <int K, int CL>
+  void operator()() const { launch_extremes<K, CL>(a, blocks, partial); }
+};
+
+struct Quantise {
+  const HshArgs& a;
+  int vout;
+  const float* qparams;
+  uint8_t* coef8;
+  template <int K, int CL>
+  void operator()() const { launch_quantise<K, CL>(a, vout, qparams, coef8); }
+};
+
+template <int K, typename TO>
+void launch_relight8(const uint8_t* coef8, int64_t P, int vin, int vout, const float* qparams,
+                     const double* luv, int E, void* out, hipStream_t s) {
+  hipLaunchKernelGGL((relight_hsh8_k<K, TO>), dim3(grid_1d(P, CHUNK)), dim3(256), 0, s, coef8, P, vin, vout,
+                     qparams, luv, E, static_cast<TO*>(out));
+}
+
+template <int K>
+void launch_relight8_out(int out_dtype, const uint8_t* coef8, int64_t P, int vin, int vout,
+                         const float* qparams, const double* luv, int E, void* out, hipStream_t s) {
+  switch (out_dtype) {
+    case RTI_F32: launch_relight8<K, float>(coef8, P, vin, vout, qparams, luv, E, out, s); break;
+    case RTI_I32: launch_relight8<K, int32_t>(coef8, P, vin, vout, qparams, luv, E, out, s); break;
+    default: launch_relight8<K, uint8_t>(coef8, P, vin, vout, qparams, luv, E, out, s); break;
+  }
+}
+
+inline bool hsh_basis(int basis) { return basis == RTI_BASIS_HSH9 || basis == RTI_BASIS_HSH16; }
+
+// the checks rti_hsh_qparams and rti_hsh_quantise share, in the order include/rti.h lists them
+int check_hsh_maps(const char* entry, int basis, int layout, int64_t stride, int64_t P) {
+  if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", entry);
+  if (!hsh_basis(basis)) return fail(RTI_ERR_UNSUPPORTED, "%s: basis %d (HSH-9 and HSH-16 only)", entry, basis);
+  if (int st = check_coef_layout(entry, layout)) return st;
+  return check_coef_stride(entry, coef_view(static_cast<const float*>(nullptr), layout, basis_terms(basis), P, stride),
+                           P, 3);
+}
+
+// pixel-major rows as 16-byte pieces: every wave's run of every channel starts on a 16-byte boundary
+inline int maps_vec(const float* coef, int layout, int64_t cs) {
+  return layout == RTI_COEF_PIXEL_MAJOR && aligned_to(coef, 16) && cs % 4 == 0 ? 1 : 0;
+}
+
+}  // namespace
+}  // namespace rti
+
+using namespace rti;
+
+extern "C" int64_t rti_hsh_qparams_workspace(int k, int64_t P) {
+  return P < 1 || (k != 9 && k != 16) ? 0 : qparams_blocks(P) * 2 * k * (int64_t)sizeof(float);
+}
+
+extern "C" int rti_hsh_qparams(const float* coef, int basis, int coef_layout, int64_t coef_channel_stride, int64_t P,
+                               void* workspace, float* qparams, rti_stream_t stream) {
+  const char* const E = "rti_hsh_qparams";
+  if (int st = check_pointers(E, {coef, workspace, qparams})) return st;
+  if (int st = check_hsh_maps(E, basis, coef_layout, coef_channel_stride, P)) return st;
+  if (!aligned_to(workspace, 4) || !aligned_to(qparams, 4))
+    return fail(RTI_ERR_BAD_ARG, "%s: workspace and qparams must be 4-byte aligned", E);
+  const int k = basis_terms(basis);
+  const int64_t cs = coef_channel_stride ? coef_channel_stride : P * k;
+  const int blocks = (int)qparams_blocks(P);
+  float* partial = static_cast<float*>(workspace);
+  const HshArgs a{coef, coef_layout, cs, P, maps_vec(coef, coef_layout, cs), (hipStream_t)stream};
+  note_launches(2);
+  with_k_layout(k, coef_layout, Extremes{a, blocks, partial});
+  if (int st = check_launch(E)) return st;
+  if (k == 9)
+    hipLaunchKernelGGL(hsh_qparams_k<9>, dim3(1), dim3(256), 0, a.s, partial, blocks, qparams);
+  else
+    hipLaunchKernelGGL(hsh_qparams_k<16>, dim3(1), dim3(256), 0, a.s, partial, blocks, qparams);
+  return check_launch(E);
+}
+
+extern "C" int rti_hsh_quantise(const float* coef, int basis, int coef_layout, int64_t coef_channel_stride, int64_t P,
+                                const float* qparams, uint8_t* coef8, rti_stream_t stream) {
+  const char* const E = "rti_hsh_quantise";
+  if (int st = check_pointers(E, {coef, qparams, coef8})) return st;
+  if (int st = check_hsh_maps(E, basis, coef_layout, coef_channel_stride, P)) return st;
+  if (!aligned_to(qparams, 4)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 4-byte aligned", E);
+  const int k = basis_terms(basis);
+  const int64_t cs = coef_channel_stride ? coef_channel_stride : P * k;
+  const HshArgs a{coef, coef_layout, cs, P, maps_vec(coef, coef_layout, cs), (hipStream_t)stream};
+  note_launches(1);
+  with_k_layout(k, coef_layout, Quantise{a, aligned_to(coef8, 16) ? 1 : 0, qparams, coef8});
+  return check_launch(E);
+}
+
+extern "C" int rti_relight_hsh8(const uint8_t* coef8, int basis, int64_t P, const float* qparams, const double* luv,
+                                int E_, void* out, int out_dtype, rti_stream_t stream) {
+  const char* const E = "rti_relight_hsh8";
+  if (int st = check_pointers(E, {coef8, qparams, luv, out})) return st;
+  if (P < 1 || E_ < 1) return fail(RTI_ERR_BAD_ARG, "%s: P and E must be positive", E);
+  if (!hsh_basis(basis)) return fail(RTI_ERR_UNSUPPORTED, "%s: basis %d (HSH-9 and HSH-16 only)", E, basis);
+  if (out_dtype != RTI_F32 && out_dtype != RTI_I32 && out_dtype != RTI_U8)
+    return fail(RTI_ERR_UNSUPPORTED, "%s: out dtype %d", E, out_dtype);
+  if (!aligned_to(qparams, 4)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 4-byte aligned", E);
+  const int vin = aligned_to(coef8, 16) ? 1 : 0;
+  // a wave's 192 output elements as dwords: direction e's rows start 3·P·e elements into out
+  const int vout = aligned_to(out, 4) && (out_dtype != RTI_U8 || P % 4 == 0) ? 1 : 0;
+  note_launches(1);
+  if (basis == RTI_BASIS_HSH9)
+    launch_relight8_out<9>(out_dtype, coef8, P, vin, vout, qparams, luv, E_, out, (hipStream_t)stream);
+  else
+    launch_relight8_out<16>(out_dtype, coef8, P, vin, vout, qparams, luv, E_, out, (hipStream_t)stream);
+  return check_launch(E);
+}

@@ -25,6 +25,10 @@ bara96/Smartphone-based-RTI: analysis.py:196-411, interactive_relighting.py:11-3
     rti.write_ptm("object.ptm", q)                   # the same file, without the fp32 copy to the host
     q = rti.read_ptm("object.ptm", quantised=True)[1].to("cuda")  # a loaded file stays 9 bytes per pixel
 
+    h = rti.quantise_hsh(rti.fit(Irgb, lu, lv, basis="hsh16"))    # RGB HSH-16 as 48 bytes per pixel
+    rgb = rti.relight_hsh8(h, 0.3, -0.2, out_dtype=torch.uint8)   # one launch, from the bytes
+    rti.write_rti("object.rti", h)                   # and back: rti.read_rti("object.rti", quantised=True)
+
 Compute runs in HIP kernels of librti.so (include/rti.h); importing this
 package does not touch the GPU.
 """
@@ -38,8 +42,10 @@ from .api import (BASES, FitAccumulator, apply_operator, basis_eval, basis_id, b
                   gauss_taps, map_unsharp_into, normals_unsharp, shade_normals, shade_normals_into, unsharp,
                   fit_lrgb, gram, lrgb_from_rgb, lrgb_from_rgb_into, lrgb_luminance, relight_lrgb, relight_lrgb_into,
                   QuantisedLRGB, dequantise_lrgb, lrgb_qparams_into, lrgb_qparams_workspace, lrgb_quantise_into,
-                  quantise_lrgb, relight_lrgb8, relight_lrgb8_into)
-from .io import read_ptm, write_ptm
+                  quantise_lrgb, relight_lrgb8, relight_lrgb8_into,
+                  QuantisedHSH, dequantise_hsh, hsh_qparams_into, hsh_qparams_workspace, hsh_quantise_into,
+                  quantise_hsh, relight_hsh8, relight_hsh8_into)
+from .io import read_ptm, read_rti, write_ptm, write_rti
 
 __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_into", "fit_chunked",
            "RTIError", "RTILibraryMissing", "apply_operator", "basis_eval", "basis_id", "basis_operator",
@@ -52,7 +58,9 @@ __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_in
            "shade_normals_into", "unsharp", "fit_lrgb", "gram", "lrgb_from_rgb", "lrgb_from_rgb_into",
            "lrgb_luminance", "relight_lrgb", "relight_lrgb_into", "QuantisedLRGB", "dequantise_lrgb",
            "lrgb_qparams_into", "lrgb_qparams_workspace", "lrgb_quantise_into", "quantise_lrgb", "relight_lrgb8",
-           "relight_lrgb8_into", "read_ptm", "write_ptm", "library_path", "load"]
+           "relight_lrgb8_into", "QuantisedHSH", "dequantise_hsh", "hsh_qparams_into", "hsh_qparams_workspace",
+           "hsh_quantise_into", "quantise_hsh", "relight_hsh8", "relight_hsh8_into", "read_ptm", "write_ptm",
+           "read_rti", "write_rti", "library_path", "load"]
 
 __version__ = "0.1.0"
 

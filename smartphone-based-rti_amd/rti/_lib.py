@@ -168,6 +168,11 @@ SIGNATURES = {
     "rti_lrgb_quantise": (_c_int, [_c_void_p, _c_int, _c_i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "rti_relight_lrgb8": (_c_int, [_c_void_p, _c_void_p, _c_i64, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int,
                                    _c_void_p]),
+    "rti_hsh_qparams_workspace": (_c_i64, [_c_int, _c_i64]),
+    "rti_hsh_qparams": (_c_int, [_c_void_p, _c_int, _c_int, _c_i64, _c_i64, _c_void_p, _c_void_p, _c_void_p]),
+    "rti_hsh_quantise": (_c_int, [_c_void_p, _c_int, _c_int, _c_i64, _c_i64, _c_void_p, _c_void_p, _c_void_p]),
+    "rti_relight_hsh8": (_c_int, [_c_void_p, _c_int, _c_i64, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int,
+                                  _c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -1525,6 +1525,222 @@ def relight_lrgb8(q, lu, lv, *, out_dtype=torch.float32):
     return out[0] if scalar else out
 
 
+# ---- 8-bit RGB HSH maps: the .rti payload on the device (rti_hsh8.hip) -------
+
+_HSH8_NAMES = {L.RTI_BASIS_HSH9: "hsh9", L.RTI_BASIS_HSH16: "hsh16"}
+_HSH8_TERMS = {L.RTI_BASIS_HSH9: 9, L.RTI_BASIS_HSH16: 16}
+
+
+def _hsh8_basis(basis):
+    """A basis name or id -> the id of HSH-9 or HSH-16; anything else is not built."""
+    b = basis_id(basis)
+    if b not in _HSH8_NAMES:
+        raise NotImplementedError(f"8-bit HSH maps are HSH-9 and HSH-16 only; got basis {basis!r}")
+    return b
+
+
+class QuantisedHSH:
+    """An 8-bit RGB HSH map: the payload of an HSH ``.rti`` file and its header values.
+
+    coef: uint8 [H, W, 3, k] or [P, 3, k], per pixel the k bytes of R, then G, then B; qparams: fp32 [2k] =
+    scale[0..k-1], bias[0..k-1], shared by the three channels; basis: "hsh9" (k = 9) or "hsh16" (k = 16).  A
+    coefficient is ``byte·(scale/255) + bias`` in fp32 (``dequantise_hsh``).  Rows top first.  Both tensors on one
+    device (the GPU, or the host for ``read_rti(path, quantised=True)``); immutable.  ``scale`` / ``bias`` copy
+    qparams to the host: they are the one accessor that synchronises."""
+    __slots__ = ("_coef", "_qparams", "_basis")
+
+    def __init__(self, coef, qparams, basis):
+        b = _hsh8_basis(basis)
+        k = _HSH8_TERMS[b]
+        if not (torch.is_tensor(coef) and torch.is_tensor(qparams)):
+            raise ValueError("QuantisedHSH takes two tensors (coef, qparams) and a basis")
+        if coef.dtype != torch.uint8 or coef.dim() < 3 or tuple(coef.shape[-2:]) != (3, k) or coef.numel() == 0 \
+                or not coef.is_contiguous():
+            raise ValueError(f"coef must be a contiguous uint8 [..., 3, {k}] tensor; got {coef.dtype} "
+                             f"{tuple(coef.shape)}")
+        if qparams.dtype != torch.float32 or tuple(qparams.shape) != (2 * k,) or not qparams.is_contiguous():
+            raise ValueError(f"qparams must be a contiguous float32 [{2 * k}] tensor; got {qparams.dtype} "
+                             f"{tuple(qparams.shape)}")
+        if coef.device != qparams.device:
+            raise ValueError(f"coef and qparams must be on one device; got {coef.device}, {qparams.device}")
+        for name, v in zip(self.__slots__, (coef, qparams, b)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("QuantisedHSH is immutable")
+
+    coef = property(lambda self: self._coef)
+    qparams = property(lambda self: self._qparams)
+    basis = property(lambda self: _HSH8_NAMES[self._basis], doc='"hsh9" or "hsh16"')
+    k = property(lambda self: _HSH8_TERMS[self._basis], doc="terms per channel: 9 or 16")
+    shape = property(lambda self: tuple(self._coef.shape[:-2]), doc="the spatial shape: (H, W) or (P,)")
+    device = property(lambda self: self._coef.device)
+
+    def _host(self):
+        return self._qparams.detach().cpu().numpy()
+
+    scale = property(lambda self: self._host()[:self.k].copy(), doc="host fp32 [k] (synchronises)")
+    bias = property(lambda self: self._host()[self.k:].copy(), doc="host fp32 [k] (synchronises)")
+
+    def to(self, device):
+        return QuantisedHSH(self._coef.to(device), self._qparams.to(device), self._basis)
+
+    def __repr__(self):
+        return f"QuantisedHSH(shape={self.shape}, basis={self.basis!r}, device={self.device})"
+
+
+def _hsh_maps(coef, k):
+    """Three contiguous CUDA fp32 HSH maps of k terms per pixel, [3, ...] -> P."""
+    _require_cuda(coef, "coef")
+    if coef.dtype != torch.float32 or not coef.is_contiguous() or coef.dim() < 2 or coef.shape[0] != 3 \
+            or coef.numel() == 0 or coef.numel() % (3 * k):
+        raise ValueError(f"coef must be three contiguous float32 maps of {k} terms per pixel, [3, ...]; got "
+                         f"{coef.dtype} {tuple(coef.shape)}")
+    return coef.numel() // (3 * k)
+
+
+def _hsh_qparams_dev(qparams, k, like):
+    _require_cuda(qparams, "qparams")
+    if qparams.dtype != torch.float32 or qparams.numel() != 2 * k or not qparams.is_contiguous() \
+            or qparams.device != like.device:
+        raise ValueError(f"qparams must be a contiguous float32 [{2 * k}] tensor on {like.device}; got "
+                         f"{qparams.dtype} {tuple(qparams.shape)} on {qparams.device}")
+    return _vp(qparams)
+
+
+def hsh_qparams_workspace(P, basis="hsh16"):
+    """Bytes of device scratch ``hsh_qparams_into`` needs for P pixels (``rti_hsh_qparams_workspace``)."""
+    n = int(L.lib().rti_hsh_qparams_workspace(_HSH8_TERMS[_hsh8_basis(basis)], int(P)))
+    if n <= 0:
+        raise ValueError(f"P must be positive; got {P}")
+    return n
+
+
+def hsh_qparams_into(coef, workspace, qparams, *, basis="hsh16", layout="pixel"):
+    """Launch ``rti_hsh_qparams`` on preallocated tensors (no allocation, graph-capturable): the k scales and k
+    biases ``write_rti`` would give the maps.
+
+    coef: contiguous CUDA fp32 [3, P, k] (layout="pixel") or [3, k, P] ("planar"), any spatial shape in place of
+    P; workspace: a contiguous CUDA tensor of at least ``hsh_qparams_workspace(P, basis)`` bytes (it need not be
+    initialised); qparams: CUDA fp32 [2k]."""
+    b = _hsh8_basis(basis)
+    k = _HSH8_TERMS[b]
+    P = _hsh_maps(coef, k)
+    _require_cuda(workspace, "workspace")
+    need = hsh_qparams_workspace(P, b)
+    if not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need \
+            or workspace.device != coef.device:
+        raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on {coef.device}; got "
+                         f"{workspace.numel() * workspace.element_size()} bytes on {workspace.device}")
+    st = L.lib().rti_hsh_qparams(_vp(coef), b, _layout_id(layout), 0, P, _vp(workspace),
+                                 _hsh_qparams_dev(qparams, k, coef), _stream_of(coef))
+    L.check(st, "rti_hsh_qparams")
+    return qparams
+
+
+def hsh_quantise_into(coef, qparams, coef8, *, basis="hsh16", layout="pixel"):
+    """Launch ``rti_hsh_quantise`` on preallocated tensors (no allocation, graph-capturable).
+
+    coef: as ``hsh_qparams_into``; qparams: CUDA fp32 [2k] (``hsh_qparams_into``); coef8: uint8 with 3·k·P
+    elements ([P, 3, k]).  Returns coef8."""
+    b = _hsh8_basis(basis)
+    k = _HSH8_TERMS[b]
+    P = _hsh_maps(coef, k)
+    st = L.lib().rti_hsh_quantise(_vp(coef), b, _layout_id(layout), 0, P, _hsh_qparams_dev(qparams, k, coef),
+                                  _map_out(coef8, "coef8", torch.uint8, 3 * k * P, coef), _stream_of(coef))
+    L.check(st, "rti_hsh_quantise")
+    return coef8
+
+
+def quantise_hsh(coef, basis="hsh16", *, layout="pixel"):
+    """Quantise three HSH maps to the 3k bytes per pixel of an .rti file on the GPU (``rti_hsh_qparams`` then
+    ``rti_hsh_quantise``): the bytes, scales and biases ``write_rti`` computes on the host, without the copy.
+
+    coef: CUDA fp32 [3, H, W, k] / [3, P, k] (layout="pixel") or [3, k, H, W] / [3, k, P] ("planar"), as ``fit``
+    returns it for a [3, N, H, W] stack.  Returns a ``QuantisedHSH`` on coef's device; ``write_rti(path, q)``
+    writes it, ``relight_hsh8`` renders it."""
+    b = _hsh8_basis(basis)
+    _require_cuda(coef, "coef")
+    k = _HSH8_TERMS[b]
+    cl = _layout_id(layout)
+    if coef.dim() < 3 or coef.shape[0] != 3:
+        raise ValueError(f"coef must be three HSH maps [3, ...]; got {tuple(coef.shape)}")
+    spatial = _coef_spatial(coef[0], k, cl)
+    m = coef.contiguous()
+    P = _hsh_maps(m, k)
+    ws = torch.empty(hsh_qparams_workspace(P, b), dtype=torch.uint8, device=m.device)
+    qparams = torch.empty(2 * k, dtype=torch.float32, device=m.device)
+    coef8 = torch.empty(spatial + (3, k), dtype=torch.uint8, device=m.device)
+    hsh_qparams_into(m, ws, qparams, basis=b, layout=cl)
+    hsh_quantise_into(m, qparams, coef8, basis=b, layout=cl)
+    return QuantisedHSH(coef8, qparams, b)
+
+
+def dequantise_hsh(q):
+    """The three fp32 HSH maps [3, ..., k] of a quantised one, with ``read_rti``'s arithmetic: step = scale/255
+    (one fp32 division per term), byte·step, + bias, each rounded to fp32.  Plain torch operations on q's device
+    (not a hot path); ``relight(dequantise_hsh(q)[c], ...)`` is channel c of ``relight_hsh8(q, ...)`` bit for
+    bit."""
+    if not isinstance(q, QuantisedHSH):
+        raise ValueError(f"q must be a QuantisedHSH; got {type(q).__name__}")
+    k = q.k
+    # A tensor divisor: division by a Python scalar may be evaluated as a product with its reciprocal.  The
+    # quotient of two fp32 values formed in fp64 and rounded to fp32 is the correctly rounded fp32 quotient
+    # (53 >= 2·24 + 2 bits), whatever a backend's fp32 division does.
+    step = (q.qparams[:k].double() / torch.full((1,), 255.0, dtype=torch.float64, device=q.device)).float()
+    c = q.coef.to(torch.float32) * step  # a separate multiply and add: no FMA
+    c = c + q.qparams[k:]
+    return c.movedim(-2, 0).contiguous()
+
+
+def relight_hsh8_into(coef8, qparams, luv_dev, out, *, basis="hsh16"):
+    """Launch ``rti_relight_hsh8`` on preallocated tensors (no allocation, graph-capturable).
+
+    coef8: contiguous CUDA uint8 [P, 3, k], any spatial shape in place of P; qparams: CUDA fp32 [2k]; luv_dev:
+    CUDA fp64 [E, 2]; out: float32, int32 or uint8 with E·P·3 elements ([E, P, 3])."""
+    b = _hsh8_basis(basis)
+    k = _HSH8_TERMS[b]
+    _require_cuda(coef8, "coef8")
+    if coef8.dtype != torch.uint8 or not coef8.is_contiguous() or coef8.numel() == 0 or coef8.numel() % (3 * k):
+        raise ValueError(f"coef8 must be a contiguous uint8 map of {3 * k} bytes per pixel; got {coef8.dtype} "
+                         f"{tuple(coef8.shape)}")
+    P = coef8.numel() // (3 * k)
+    _require_cuda(luv_dev, "luv")
+    if luv_dev.dtype != torch.float64 or luv_dev.dim() != 2 or luv_dev.shape[1] != 2 or luv_dev.shape[0] < 1 \
+            or not luv_dev.is_contiguous() or luv_dev.device != coef8.device:
+        raise ValueError(f"luv must be a contiguous float64 [E, 2] tensor on {coef8.device}; got {luv_dev.dtype} "
+                         f"{tuple(luv_dev.shape)} on {luv_dev.device}")
+    E = luv_dev.shape[0]
+    odt = _ENHANCED_DTYPES.get(out.dtype) if torch.is_tensor(out) else None
+    if odt is None:
+        raise ValueError("out must be a float32, int32 or uint8 tensor")
+    st = L.lib().rti_relight_hsh8(_vp(coef8), b, P, _hsh_qparams_dev(qparams, k, coef8), _vp(luv_dev), E,
+                                  _map_out(out, "out", out.dtype, E * P * 3, coef8), odt, _stream_of(coef8))
+    L.check(st, "rti_relight_hsh8")
+    return out
+
+
+def relight_hsh8(q, lu, lv, *, out_dtype=torch.float32):
+    """Relight a quantised RGB HSH map to RGB images on the GPU in one launch (``rti_relight_hsh8``), reading 3k
+    bytes per pixel once for every direction.  Channel c of the images equals
+    ``relight(dequantise_hsh(q)[c], lu, lv, basis=q.basis)`` bit for bit.
+
+    q: a ``QuantisedHSH`` on the GPU.  lu, lv: scalars or E directions.  Returns [E, H, W, 3], squeezed to
+    [H, W, 3] for scalar directions, in out_dtype: float32, or int32 / uint8 converted as ``relight`` does."""
+    if not isinstance(q, QuantisedHSH):
+        raise ValueError(f"q must be a QuantisedHSH (quantise_hsh, or read_rti(path, quantised=True)); got "
+                         f"{type(q).__name__}")
+    _require_cuda(q.coef, "q.coef")
+    if out_dtype not in _ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    scalar = np.ndim(lu) == 0 and np.ndim(lv) == 0
+    luv = np.stack([np.asarray(lu, np.float64).ravel(), np.asarray(lv, np.float64).ravel()], -1)
+    luv_d = torch.as_tensor(np.ascontiguousarray(luv), device=q.device)
+    out = torch.empty((luv.shape[0],) + q.shape + (3,), dtype=out_dtype, device=q.device)
+    relight_hsh8_into(q.coef, q.qparams, luv_d, out, basis=q._basis)
+    return out[0] if scalar else out
+
+
 # ---- light operators (RBF, fused PTM/HSH fit + evaluation) ----------------------------------
 
 def _query(qu, qv):

@@ -266,3 +266,174 @@ def read_ptm(path, quantised=False):
         return fmt, np.concatenate([coef, rgb], -1).astype(np.float32)
     coef = (data[:18 * n].reshape(3, H, W, 6)[:, ::-1].astype(np.float64) - bias) * scale
     return fmt, coef.astype(np.float32)
+
+
+# ---- .rti files (HSH 1.2, uncompressed RGB hemispherical harmonics; layout restated in DESIGN.md §4.9) --------
+#   ASCII lines; a line that starts with '#' after the first is a comment:
+#     #HSH1.2
+#     3                 the RTI file type: HSH
+#     W H 3             width, height, colour channels
+#     k 2 1             terms per channel (9 or 16), basis type (2 = HSH), bytes per element
+#   then k little-endian fp32 scales and k little-endian fp32 biases, shared by the three channels
+#   then H·W·3·k payload bytes: rows top first, per pixel the k bytes of R, then of G, then of B;
+#     coefficient = (float)raw·(scale_j/255) + bias_j in fp32, term j = column j of rti_basis_eval
+#   No file of another writer was available to this build: the row order, and the order and signs of the
+#   sin / cos terms relative to other HSH writers, are this build's restatement and unverified.  Each is one
+#   constant below.
+_RTI_MAGIC = b"#HSH1.2"
+_RTI_TYPE_HSH = 3
+_RTI_BASIS_HSH = 2
+_RTI_ROW_STEP = 1                    # 1: the file's first row is the map's top row; -1 would store bottom first
+_RTI_TERM_ORDER = tuple(range(16))   # file term i of a pixel is column _RTI_TERM_ORDER[i] of rti_basis_eval
+_RTI_BASES = {9: "hsh9", 16: "hsh16"}
+
+
+def _rti_terms(basis):
+    from .api import _HSH8_TERMS, _hsh8_basis
+
+    return _HSH8_TERMS[_hsh8_basis(basis)]
+
+
+def hsh_qparams_host(m):
+    """m fp32 [3, ..., k] -> (scale fp32 [k], bias fp32 [k]), rti_hsh_qparams' arithmetic (include/rti.h): over
+    the finite values of term j in the three channels, bias = lo (a zero as +0), scale = hi − lo in fp32 where
+    that is finite and > 0, else 1; a term without a finite value gets (1, 0)."""
+    k = m.shape[-1]
+    scale, bias = np.ones(k, np.float32), np.zeros(k, np.float32)
+    with np.errstate(all="ignore"):
+        for j in range(k):
+            x = m[..., j]
+            fin = x[np.isfinite(x)]
+            if fin.size:
+                lo, hi = np.float32(fin.min()), np.float32(fin.max())
+                bias[j] = lo + np.float32(0.0)
+                d = np.float32(hi - lo)
+                if np.isfinite(d) and d > 0:
+                    scale[j] = d
+    return scale, bias
+
+
+def hsh_quantise_host(m, scale, bias):
+    """m fp32 [..., k] -> uint8 of the same shape, rti_hsh_quantise's arithmetic: step = scale/255 in fp32, then
+    raw = clip(rint((x − bias)/step), 0, 255) in fp64; a NaN writes 0, ±inf saturates."""
+    with np.errstate(all="ignore"):
+        step = np.asarray(scale, np.float32) / np.float32(255.0)
+        t = (m.astype(np.float64) - np.asarray(bias, np.float32).astype(np.float64)) / step.astype(np.float64)
+        raw = np.clip(np.rint(t), 0.0, 255.0)
+        return np.where(np.isnan(t), 0.0, raw).astype(np.uint8)
+
+
+def hsh_dequantise_host(raw, scale, bias):
+    """uint8 [..., k] -> fp32, the map read_rti builds: (float)raw·(scale/255) + bias, every operation in fp32."""
+    with np.errstate(all="ignore"):
+        step = np.asarray(scale, np.float32) / np.float32(255.0)
+        t = raw.astype(np.float32) * step
+        return (t + np.asarray(bias, np.float32)).astype(np.float32)
+
+
+def write_rti(path, maps, basis="hsh16"):
+    """Write an uncompressed HSH ``.rti`` file (``#HSH1.2``, RGB, one byte per coefficient).
+
+    maps: a ``QuantisedHSH`` [H, W] (``quantise_hsh``, or ``read_rti(path, quantised=True)``), whose bytes and
+    2k floats are copied to the host and written as they are (its own basis is used); or three fp32 maps
+    [3, H, W, k] (``fit`` of a colour stack with an HSH basis), an array or a tensor on any device, quantised on
+    the host with the arithmetic of ``rti_hsh_qparams`` / ``rti_hsh_quantise``, so both routes write the same
+    file.  The header holds the scales and biases as binary fp32: a round trip through a file is exact.  Returns
+    path."""
+    from .api import QuantisedHSH
+
+    if isinstance(maps, QuantisedHSH):
+        if len(maps.shape) != 2:
+            raise ValueError(f"a file needs a map with rows: QuantisedHSH [H, W]; got {maps.shape}")
+        k = maps.k
+        raw, scale, bias = maps.coef.detach().cpu().numpy(), maps.scale, maps.bias
+    else:
+        k = _rti_terms(basis)
+        if hasattr(maps, "detach"):
+            maps = maps.detach().cpu().numpy()
+        m = np.asarray(maps, dtype=np.float32)
+        if m.ndim != 4 or m.shape[0] != 3 or m.shape[3] != k:
+            raise ValueError(f"RGB HSH maps are [3, H, W, {k}]; got {m.shape}")
+        if m.shape[1] < 1 or m.shape[2] < 1:
+            raise ValueError(f"empty map {m.shape}")
+        scale, bias = hsh_qparams_host(m)
+        raw = hsh_quantise_host(m, scale, bias).transpose(1, 2, 0, 3)
+    H, W = raw.shape[:2]
+    order = list(_RTI_TERM_ORDER[:k])
+    head = b"\n".join([_RTI_MAGIC, b"%d" % _RTI_TYPE_HSH, b"%d %d 3" % (W, H), b"%d %d 1" % (k, _RTI_BASIS_HSH)])
+    with open(path, "wb") as f:
+        f.write(head + b"\n")
+        f.write(np.asarray(scale, np.float32)[order].astype("<f4").tobytes())
+        f.write(np.asarray(bias, np.float32)[order].astype("<f4").tobytes())
+        f.write(np.ascontiguousarray(raw[::_RTI_ROW_STEP][..., order]).tobytes())
+    return path
+
+
+def _rti_line(buf, pos, what):
+    """The next header line of buf from pos (comment lines skipped) as integer tokens, and the offset after it."""
+    while True:
+        end = buf.find(b"\n", pos)
+        if end < 0:
+            raise ValueError(f"RTI header ends early ({what})")
+        line, pos = buf[pos:end].strip(), end + 1
+        if not line.startswith(b"#"):
+            break
+    try:
+        return [int(t) for t in line.split()], pos
+    except ValueError:
+        raise ValueError(f"malformed RTI header ({what}): {line[:32]!r}") from None
+
+
+def read_rti(path, quantised=False):
+    """Read an uncompressed HSH ``.rti`` file -> ``(basis, maps)``: ("hsh9" | "hsh16", fp32 [3, H, W, k]), rows
+    top first as ``write_rti`` takes them, each coefficient (float)raw·(scale/255) + bias in fp32.
+
+    quantised=True keeps the file's 3k bytes per pixel: (basis, ``QuantisedHSH`` [H, W]) of host tensors with
+    the header's scales and biases; ``.to(device)`` moves it to the GPU for ``relight_hsh8``.
+
+    A bad magic, a short payload, W or H < 1 or a channel count other than 3 raise ValueError; a term count other
+    than 9 / 16, a basis type other than 2 (HSH), an element size other than 1 and the other RTI file types raise
+    NotImplementedError."""
+    with open(path, "rb") as f:
+        buf = f.read()
+    end = buf.find(b"\n")
+    if buf[:end if end >= 0 else len(buf)].strip() != _RTI_MAGIC:
+        raise ValueError(f"not an HSH 1.2 .rti file: magic {buf[:16]!r}")
+    ftype, pos = _rti_line(buf, end + 1, "file type")
+    if len(ftype) != 1:
+        raise ValueError(f"malformed RTI header (file type): {ftype}")
+    if ftype[0] != _RTI_TYPE_HSH:
+        raise NotImplementedError(f"RTI file type {ftype[0]} is not built (3 = HSH only)")
+    size, pos = _rti_line(buf, pos, "size")
+    terms, pos = _rti_line(buf, pos, "basis")
+    if len(size) != 3 or len(terms) != 3:
+        raise ValueError(f"malformed RTI header: size {size}, basis {terms}")
+    (W, H, C), (k, btype, esize) = size, terms
+    if W < 1 or H < 1:
+        raise ValueError(f"RTI header: bad size {W} x {H}")
+    if C != 3:
+        raise ValueError(f"RTI header: {C} colour channels (3 expected)")
+    if btype != _RTI_BASIS_HSH:
+        raise NotImplementedError(f"RTI basis type {btype} is not built (2 = HSH only)")
+    if esize != 1:
+        raise NotImplementedError(f"RTI element size {esize} is not built (1 byte only)")
+    if k not in _RTI_BASES:
+        raise NotImplementedError(f"{k} HSH terms are not built (9 and 16 only)")
+    need = 8 * k + H * W * 3 * k
+    if len(buf) - pos < need:
+        raise ValueError(f"short RTI payload: {max(len(buf) - pos, 0)} of {need} bytes")
+    order = list(_RTI_TERM_ORDER[:k])
+    qp = np.frombuffer(buf, "<f4", 2 * k, pos).astype(np.float32).reshape(2, k)
+    scale, bias = np.empty(k, np.float32), np.empty(k, np.float32)
+    scale[order], bias[order] = qp[0], qp[1]
+    data = np.frombuffer(buf, np.uint8, H * W * 3 * k, pos + 8 * k).reshape(H, W, 3, k)[::_RTI_ROW_STEP]
+    raw = np.empty((H, W, 3, k), np.uint8)
+    raw[..., order] = data
+    if quantised:
+        import torch
+
+        from .api import QuantisedHSH
+
+        return _RTI_BASES[k], QuantisedHSH(torch.from_numpy(raw), torch.from_numpy(np.concatenate([scale, bias])),
+                                           _RTI_BASES[k])
+    return _RTI_BASES[k], np.ascontiguousarray(hsh_dequantise_host(raw, scale, bias).transpose(2, 0, 1, 3))

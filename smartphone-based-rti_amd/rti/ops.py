@@ -1,7 +1,7 @@
 """PyTorch custom ops over the C ABI: ``torch.ops.rti.fit_shared`` / ``fit_shared_residual`` /
 ``fit_robust`` / ``fit_accumulate`` / ``fit_accum_solve`` / ``fit_residual`` / ``relight`` / ``ptm_normals`` /
 ``relight_enhanced`` / ``map_unsharp`` / ``shade_normals`` / ``lrgb_from_rgb`` / ``relight_lrgb`` /
-``lrgb_quantise`` / ``relight_lrgb8``.
+``lrgb_quantise`` / ``relight_lrgb8`` / ``hsh_quantise`` / ``relight_hsh8``.
 
 They let the fit and relight kernels sit inside torch programs (and
 ``torch.library`` fake-tensor tracing) while the compute stays in librti's
@@ -419,4 +419,50 @@ def relight_lrgb8(coef8: torch.Tensor, rgb8: torch.Tensor, qparams: torch.Tensor
 
 @relight_lrgb8.register_fake
 def _(coef8, rgb8, qparams, luv, out_dtype=torch.float32):
+    return coef8.new_empty((luv.shape[0], coef8.shape[0], 3), dtype=out_dtype)
+
+
+@torch.library.custom_op("rti::hsh_quantise", mutates_args=())
+def hsh_quantise(coef: torch.Tensor, k: int = 16, planar: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+    """Three HSH maps -> their .rti bytes and header values (``rti_hsh_qparams`` then ``rti_hsh_quantise``).  coef
+    CUDA fp32 [3, P, k] (or [3, k, P] if planar), k = 9 or 16 -> (coef8 uint8 [P, 3, k], qparams fp32 [2k])."""
+    api._require_cuda(coef, "coef")
+    if k not in (9, 16):
+        raise NotImplementedError(f"8-bit HSH maps are HSH-9 and HSH-16 only; got k = {k}")
+    if coef.dim() != 3 or coef.shape[0] != 3 or coef.shape[1 if planar else 2] != k:
+        raise ValueError(f"coef must be {f'[3, {k}, P]' if planar else f'[3, P, {k}]'}; got {tuple(coef.shape)}")
+    P = coef.shape[2 if planar else 1]
+    basis, layout = f"hsh{k}", "planar" if planar else "pixel"
+    m = coef.contiguous()
+    ws = coef.new_empty((api.hsh_qparams_workspace(P, basis),), dtype=torch.uint8)
+    qparams = coef.new_empty((2 * k,), dtype=torch.float32)
+    coef8 = coef.new_empty((P, 3, k), dtype=torch.uint8)
+    api.hsh_qparams_into(m, ws, qparams, basis=basis, layout=layout)
+    api.hsh_quantise_into(m, qparams, coef8, basis=basis, layout=layout)
+    return coef8, qparams
+
+
+@hsh_quantise.register_fake
+def _(coef, k=16, planar=False):
+    P = coef.shape[2 if planar else 1]
+    return coef.new_empty((P, 3, k), dtype=torch.uint8), coef.new_empty((2 * k,), dtype=torch.float32)
+
+
+@torch.library.custom_op("rti::relight_hsh8", mutates_args=())
+def relight_hsh8(coef8: torch.Tensor, qparams: torch.Tensor, luv: torch.Tensor,
+                 out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """RGB images of a quantised RGB HSH map (``rti_relight_hsh8``).  coef8 CUDA uint8 [P, 3, k] with k = 9 or
+    16, qparams fp32 [2k], luv [E, 2] -> [E, P, 3] in out_dtype (float32, int32 or uint8)."""
+    api._require_cuda(coef8, "coef8")
+    if coef8.dim() != 3 or coef8.shape[1] != 3 or coef8.shape[2] not in (9, 16):
+        raise ValueError(f"coef8 must be [P, 3, 9] or [P, 3, 16]; got {tuple(coef8.shape)}")
+    if out_dtype not in api._ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    luv_d = luv.detach().to(device=coef8.device, dtype=torch.float64).contiguous()
+    out = coef8.new_empty((luv.shape[0], coef8.shape[0], 3), dtype=out_dtype)
+    return api.relight_hsh8_into(coef8.contiguous(), qparams.contiguous(), luv_d, out, basis=f"hsh{coef8.shape[2]}")
+
+
+@relight_hsh8.register_fake
+def _(coef8, qparams, luv, out_dtype=torch.float32):
     return coef8.new_empty((luv.shape[0], coef8.shape[0], 3), dtype=out_dtype)
