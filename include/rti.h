@@ -737,6 +737,68 @@ int rti_hsh_quantise(const float* coef, int basis, int coef_layout, int64_t coef
 int rti_relight_hsh8(const uint8_t* coef8, int basis, int64_t P, const float* qparams,
                      const double* luv, int E, void* out, int out_dtype, rti_stream_t stream);
 
+/* ---- device: HSH surface normals, a peak-direction search (rti_hsh_normals.hip) -------------------
+ * What a fitted HSH map says about the surface: the light direction at which the fitted function peaks, the
+ * analogue of rti_ptm_normals for a basis without a closed-form maximum.  It is found by evaluating the function
+ * on a grid of directions and one parabolic step; the semantics are build-defined.  Every
+ * expression below is evaluated left to right as written, every operation rounded, nothing contracted except
+ * the fused multiply-adds named.
+ *   luminance map   one map (C = 1): l_j = c_j.  Three maps (C = 3): l_j = (wR·r_j + wG·g_j) + wB·b_j in fp32,
+ *                   two products and two sums.  w: three fp32 weights on the HOST, NULL = (0.299f, 0.587f,
+ *                   0.114f).  For the 8-bit map r_j, g_j, b_j are the dequantised c_j = (float)raw_j·step_j +
+ *                   bias_j of rti_hsh8.hip above.
+ *   grid            G = grid in [4, 16].  The points are the integer pairs (i, j), −G <= i, j <= G, with
+ *                   i² + j² <= G² (this integer test is the mask), numbered e = 0..E−1 with j ascending, then
+ *                   i ascending; point e lies at (u, v) = ((double)i/(double)G, (double)j/(double)G).
+ *   value           V_e = rti_relight's F32 value of the luminance map at (u, v), bit for bit: the same
+ *                   basis_eval<float> of ((float)u, (float)v) and the same chain acc = l_0·b_0,
+ *                   acc = fmaf(l_j, b_j, acc) for j = 1..k−1.
+ *   peak            e* = the point with the largest V, the smallest e among equals; V0 = V_e*.
+ *   refinement      in fp64 from the fp32 values.  Along u, with Vm, Vp the values at (i−1, j) and (i+1, j): if
+ *                   both points lie inside the mask and d = (Vm − 2·V0) + Vp < 0, then
+ *                   δu = min(max(0.5·(Vm − Vp)/d, −0.5), 0.5), otherwise δu = 0; δv likewise along j.
+ *                   u0 = ((double)i + δu)/(double)G, v0 likewise, r² = u0·u0 + v0·v0.
+ *   kind 0  r² <= 1:                     n = (u0, v0, sqrt(1 − r²))
+ *   kind 1  r² > 1:                      n = (u0/sqrt(r²), v0/sqrt(r²), 0)
+ *   kind 2  the largest and the smallest V of the grid are equal (a flat function, e.g. an all-zero pixel):
+ *                                        n = (0, 0, 1)
+ *   kind 4  an l_j that is not finite:   n and peak are NaN              (3 is not used: rti_ptm_normals' numbers)
+ *   peak = V0, the fp32 grid maximum (an albedo proxy, as the PTM peak is); normals are rounded once to fp32.
+ * rti_peak_grid_points: E for a grid, or -1 outside [4, 16] (49 at G = 4, 317 at G = 10, 797 at G = 16).
+ * rti_peak_table_bytes: the size of the table of (basis, grid); 0 for a basis other than HSH-9 / HSH-16 or a grid
+ *   outside [4, 16].
+ * rti_peak_table: fills `table` (device, 16-byte aligned, rti_peak_table_bytes long) with the basis values of the
+ *   E grid points, formed by the device basis_eval<float> that rti_relight runs.  The buffer is opaque; one table
+ *   serves any number of maps of that (basis, grid).  One launch.
+ * rti_hsh_normals: coef: device fp32, C = 1 or 3 maps as rti_fit_shared writes them: [c][p][k]
+ *   (RTI_COEF_PIXEL_MAJOR) or [c][k][p] (RTI_COEF_PLANAR), coef_channel_stride in elements, 0 = dense = k·P (one
+ *   map never uses it).  4·C·k bytes in and 12 (+ 1 + 4) out per pixel; P·E·k fused multiply-adds.
+ * rti_hsh8_normals: coef8 / qparams as rti_relight_hsh8 takes them.  3k bytes in per pixel.
+ * Both: normals: device fp32, normal_layout [p][3] or [3][p]; kind: NULL or device uint8 [P]; peak: NULL or
+ *   device fp32 [P], as rti_ptm_normals.  The result of rti_hsh8_normals equals rti_hsh_normals' of the
+ *   dequantised maps bit for bit.
+ * All: device pointers, stream-ordered, no allocation, no synchronisation, capturable in a hipGraph; one launch.
+ * Every argument check answers before any HIP call.  RTI_ERR_BAD_ARG: a null pointer (kind, peak and w may be
+ * null); P < 1; C other than 1 or 3; a channel stride below dense (C = 3); a bad coefficient or normal layout; a
+ * grid outside [4, 16]; a non-finite weight; a table off 16 bytes or qparams off 4.  RTI_ERR_UNSUPPORTED: a basis
+ * other than HSH-9 / HSH-16 (PTM-6 has rti_ptm_normals).
+ * A lane owns two pixels, a wave two runs of 64 consecutive pixels.  The fast loads move a full run as whole
+ * 16-byte pieces through LDS and need: pixel-major fp32 maps 16-byte aligned with (C = 3) a channel stride that is
+ * a multiple of 4; coef8 16-byte aligned.  Planar maps are read per lane, coalesced as they are.  Anything else,
+ * and the last partial run, loads and stores per lane through the same per-pixel arithmetic and gives the same
+ * bits. */
+int     rti_peak_grid_points(int grid);
+int64_t rti_peak_table_bytes(int basis, int grid);
+int     rti_peak_table(int basis, int grid, void* table, rti_stream_t stream);
+int     rti_hsh_normals(const float* coef, int basis, int coef_layout, int C, int64_t coef_channel_stride,
+                        int64_t P, const float* w /* NULL ok */, int grid, const void* table,
+                        float* normals, int normal_layout, uint8_t* kind /* NULL ok */, float* peak /* NULL ok */,
+                        rti_stream_t stream);
+int     rti_hsh8_normals(const uint8_t* coef8, int basis, int64_t P, const float* qparams, const float* w /* NULL ok */,
+                         int grid, const void* table,
+                         float* normals, int normal_layout, uint8_t* kind /* NULL ok */, float* peak /* NULL ok */,
+                         rti_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -29,15 +29,13 @@
 
 #include "rti_basis.h"
 #include "rti_convert.h"
-#include "rti_lrgb_px.h"
+#include "rti_hsh_px.h"
 #include "rti_stack.h"
 
 namespace rti {
 namespace {
 
-using lrgb_px::wave_lds_sync;
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+using namespace hsh_px;  // the chain, the slab runs and the dequantisation, shared with rti_hsh_normals.hip
 
 constexpr int ECH = 64;             // directions per basis table in LDS (rti_relight's)
 constexpr int QP_MAX_BLOCKS = 768;  // the extremes' grid: 3 workgroups per CU of 256, each striding over chunks
@@ -46,91 +44,6 @@ constexpr int CHUNK = 256;          // pixels of a workgroup
 inline int64_t qparams_blocks(int64_t P) {
   const int64_t chunks = (P + CHUNK - 1) / CHUNK;
   return chunks < QP_MAX_BLOCKS ? chunks : QP_MAX_BLOCKS;
-}
-
-// rti_relight.hip's dot_k for fp32: fused multiply-adds in term order.  A copy, as rti_lrgb_px.h's loads are:
-// bench.py hashes rti_relight.hip to decide whether profiles/traffic.json is stale.
-template <int K>
-__device__ __forceinline__ float dot_k(const float (&c)[K], const float* b) {
-  float acc = c[0] * b[0];
-#pragma unroll
-  for (int k = 1; k < K; ++k) acc = fmaf(c[k], b[k], acc);
-  return acc;
-}
-
-// ---- a wave's run of 64 rows of ROWB bytes through its slab ---------------------------------------------------
-// 64·ROWB is a multiple of 16 for every ROWB; the run's base must be 16-byte aligned.  The slab is only ever
-// accessed as uint32_t / u32x4 / bytes, with a wave-level release / acquire between its phases.
-
-template <int ROWB>
-constexpr int run_v4() { return 64 * ROWB / 16; }
-// + one piece: k = 9's realigning read (lane_words) takes one dword past the run
-constexpr int slab_v4(int a, int b) { return (a > b ? a : b) + 1; }
-
-template <int ROWB>
-__device__ __forceinline__ void run_in(const void* __restrict__ g, int lane, u32x4* __restrict__ slab) {
-  constexpr int NV = run_v4<ROWB>(), PIECES = (NV + 63) / 64;
-  const u32x4* g4 = static_cast<const u32x4*>(g);
-  u32x4 t[PIECES];
-#pragma unroll
-  for (int j = 0; j < PIECES; ++j)
-    if (j * 64 + lane < NV) t[j] = __builtin_nontemporal_load(g4 + j * 64 + lane);
-#pragma unroll
-  for (int j = 0; j < PIECES; ++j)
-    if (j * 64 + lane < NV) slab[j * 64 + lane] = t[j];
-  wave_lds_sync();
-}
-
-template <int ROWB>
-__device__ __forceinline__ void run_out(void* __restrict__ g, int lane, const u32x4* __restrict__ slab) {
-  constexpr int NV = run_v4<ROWB>(), PIECES = (NV + 63) / 64;
-  wave_lds_sync();
-  u32x4* g4 = static_cast<u32x4*>(g);
-#pragma unroll
-  for (int j = 0; j < PIECES; ++j)
-    if (j * 64 + lane < NV) g4[j * 64 + lane] = slab[j * 64 + lane];
-  wave_lds_sync();  // the slab may be written again
-}
-
-// the lane's row of NB bytes out of the slab as (NB + 3) / 4 dwords, byte i of the row in byte i % 4 of word i / 4
-template <int NB>
-__device__ __forceinline__ void lane_words(const u32x4* __restrict__ slab, int lane, uint32_t (&w)[(NB + 3) / 4]) {
-  constexpr int NW = (NB + 3) / 4;
-  if constexpr (NB % 16 == 0) {
-#pragma unroll
-    for (int j = 0; j < NB / 16; ++j) {
-      const u32x4 t = slab[lane * (NB / 16) + j];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) w[4 * j + i] = t[i];
-    }
-  } else {
-    const uint32_t* s = reinterpret_cast<const uint32_t*>(slab);
-    const int o = NB * lane, d0 = o >> 2, sh = 8 * (o & 3);
-    uint32_t d[NW + 1];
-#pragma unroll
-    for (int i = 0; i <= NW; ++i) d[i] = s[d0 + i];
-#pragma unroll
-    for (int i = 0; i < NW; ++i) w[i] = (uint32_t)((((uint64_t)d[i + 1] << 32) | d[i]) >> sh);
-  }
-  wave_lds_sync();  // every lane has its row: the slab may be written again
-}
-
-// the lane's row of NB bytes (packed as lane_words returns them) into the slab
-template <int NB>
-__device__ __forceinline__ void put_lane_words(u32x4* __restrict__ slab, int lane, const uint32_t (&w)[(NB + 3) / 4]) {
-  if constexpr (NB % 16 == 0) {
-#pragma unroll
-    for (int j = 0; j < NB / 16; ++j) {
-      u32x4 t;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) t[i] = w[4 * j + i];
-      slab[lane * (NB / 16) + j] = t;
-    }
-  } else {
-    uint8_t* s = reinterpret_cast<uint8_t*>(slab) + NB * lane;
-#pragma unroll
-    for (int i = 0; i < NB; ++i) s[i] = (uint8_t)(w[i >> 2] >> (8 * (i & 3)));
-  }
 }
 
 // ---- the three fp32 maps of a pixel -----------------------------------------------------------------------------
@@ -245,18 +158,7 @@ hsh_qparams_k(const float* __restrict__ partial, int n, float* __restrict__ qpar
   }
 }
 
-// ---- per-pixel quantisation and dequantisation ------------------------------------------------------------------
-
-// step[0..K-1] = scale_j / 255.0f (one correctly rounded fp32 division per term and workgroup), bias[0..K-1];
-// the caller synchronises the workgroup
-template <int K>
-__device__ __forceinline__ void load_steps(const float* __restrict__ qparams, float* __restrict__ qs) {
-#pragma clang fp contract(off)
-  if (threadIdx.x < K) {
-    qs[threadIdx.x] = qparams[threadIdx.x] / 255.0f;
-    qs[K + threadIdx.x] = qparams[K + threadIdx.x];
-  }
-}
+// ---- per-pixel quantisation (load_steps and dequantise_px: rti_hsh_px.h) ----------------------------------------
 
 // rint(t) clipped to a byte; NaN -> 0
 __device__ __forceinline__ uint32_t byte_of(double t) {
@@ -278,24 +180,6 @@ __device__ __forceinline__ void quantise_px(const float (&x)[3][K], const float*
     for (int c = 0; c < 3; ++c) {
       const int i = c * K + j;
       w[i >> 2] |= byte_of(((double)x[c][j] - bias) / step) << (8 * (i & 3));
-    }
-  }
-}
-
-// 3K bytes -> the fp32 coefficients read_rti builds from them: a multiply and an add, each rounded
-template <int K>
-__device__ __forceinline__ void dequantise_px(const uint32_t (&w)[(3 * K + 3) / 4], const float* __restrict__ qs,
-                                              float (&c)[3][K]) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    const float step = qs[j], bias = qs[K + j];
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      const int i = ch * K + j;
-      const float raw = (float)((w[i >> 2] >> (8 * (i & 3))) & 0xffu);
-      const float t = raw * step;
-      c[ch][j] = t + bias;
     }
   }
 }
@@ -468,8 +352,6 @@ void launch_relight8_out(int out_dtype, const uint8_t* coef8, int64_t P, int vin
     default: launch_relight8<K, uint8_t>(coef8, P, vin, vout, qparams, luv, E, out, s); break;
   }
 }
-
-inline bool hsh_basis(int basis) { return basis == RTI_BASIS_HSH9 || basis == RTI_BASIS_HSH16; }
 
 // the checks rti_hsh_qparams and rti_hsh_quantise share, in the order include/rti.h lists them
 int check_hsh_maps(const char* entry, int basis, int layout, int64_t stride, int64_t P) {

@@ -28,6 +28,8 @@ bara96/Smartphone-based-RTI: analysis.py:196-411, interactive_relighting.py:11-3
     h = rti.quantise_hsh(rti.fit(Irgb, lu, lv, basis="hsh16"))    # RGB HSH-16 as 48 bytes per pixel
     rgb = rti.relight_hsh8(h, 0.3, -0.2, out_dtype=torch.uint8)   # one launch, from the bytes
     rti.write_rti("object.rti", h)                   # and back: rti.read_rti("object.rti", quantised=True)
+    n, albedo = rti.hsh8_normals(h, return_peak=True)             # where each pixel's HSH function peaks
+    img = rti.shade_normals(rti.normals_unsharp(n, 2.0, 1.5), 0.3, -0.2, albedo=albedo, ks=150, exp=75)
 
 Compute runs in HIP kernels of librti.so (include/rti.h); importing this
 package does not touch the GPU.
@@ -44,7 +46,8 @@ from .api import (BASES, FitAccumulator, apply_operator, basis_eval, basis_id, b
                   QuantisedLRGB, dequantise_lrgb, lrgb_qparams_into, lrgb_qparams_workspace, lrgb_quantise_into,
                   quantise_lrgb, relight_lrgb8, relight_lrgb8_into,
                   QuantisedHSH, dequantise_hsh, hsh_qparams_into, hsh_qparams_workspace, hsh_quantise_into,
-                  quantise_hsh, relight_hsh8, relight_hsh8_into)
+                  quantise_hsh, relight_hsh8, relight_hsh8_into,
+                  hsh8_normals, hsh8_normals_into, hsh_normals, hsh_normals_into, peak_grid_points, peak_table)
 from .io import read_ptm, read_rti, write_ptm, write_rti
 
 __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_into", "fit_chunked",
@@ -59,7 +62,8 @@ __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_in
            "lrgb_luminance", "relight_lrgb", "relight_lrgb_into", "QuantisedLRGB", "dequantise_lrgb",
            "lrgb_qparams_into", "lrgb_qparams_workspace", "lrgb_quantise_into", "quantise_lrgb", "relight_lrgb8",
            "relight_lrgb8_into", "QuantisedHSH", "dequantise_hsh", "hsh_qparams_into", "hsh_qparams_workspace",
-           "hsh_quantise_into", "quantise_hsh", "relight_hsh8", "relight_hsh8_into", "read_ptm", "write_ptm",
+           "hsh_quantise_into", "quantise_hsh", "relight_hsh8", "relight_hsh8_into", "hsh8_normals",
+           "hsh8_normals_into", "hsh_normals", "hsh_normals_into", "peak_grid_points", "peak_table", "read_ptm", "write_ptm",
            "read_rti", "write_rti", "library_path", "load"]
 
 __version__ = "0.1.0"

@@ -173,6 +173,13 @@ SIGNATURES = {
     "rti_hsh_quantise": (_c_int, [_c_void_p, _c_int, _c_int, _c_i64, _c_i64, _c_void_p, _c_void_p, _c_void_p]),
     "rti_relight_hsh8": (_c_int, [_c_void_p, _c_int, _c_i64, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int,
                                   _c_void_p]),
+    "rti_peak_grid_points": (_c_int, [_c_int]),
+    "rti_peak_table_bytes": (_c_i64, [_c_int, _c_int]),
+    "rti_peak_table": (_c_int, [_c_int, _c_int, _c_void_p, _c_void_p]),
+    "rti_hsh_normals": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_void_p, _c_int, _c_void_p,
+                                 _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "rti_hsh8_normals": (_c_int, [_c_void_p, _c_int, _c_i64, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p,
+                                  _c_int, _c_void_p, _c_void_p, _c_void_p]),
 }
 
 _lock = threading.Lock()

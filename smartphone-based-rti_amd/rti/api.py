@@ -1741,6 +1741,181 @@ def relight_hsh8(q, lu, lv, *, out_dtype=torch.float32):
     return out[0] if scalar else out
 
 
+# ---- HSH surface normals: a peak-direction search (rti_hsh_normals.hip) ------
+
+_PEAK_TABLES = {}
+
+
+def peak_grid_points(grid):
+    """E, the number of grid directions of ``grid`` in [4, 16] (``rti_peak_grid_points``)."""
+    E = int(L.lib().rti_peak_grid_points(int(grid)))
+    if E < 0:
+        raise ValueError(f"grid must lie in [4, 16]; got {grid}")
+    return E
+
+
+def peak_table(basis, grid, device):
+    """The basis values of the grid directions of (basis, grid) on ``device`` (``rti_peak_table``): an opaque
+    uint8 tensor, built once per (basis, grid, device) and kept.  The first call launches one small kernel and
+    waits for it, so make it before a graph capture; later calls return the kept tensor."""
+    b = _hsh8_basis(basis)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError("device must be a CUDA (HIP) device: librti runs only on the GPU, there is no CPU path")
+    peak_grid_points(grid)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    key = (b, int(grid), dev.index)
+    t = _PEAK_TABLES.get(key)
+    if t is None:
+        t = torch.empty(int(L.lib().rti_peak_table_bytes(b, int(grid))), dtype=torch.uint8, device=dev)
+        L.check(L.lib().rti_peak_table(b, int(grid), _vp(t), _stream_of(t)), "rti_peak_table")
+        torch.cuda.current_stream(dev).synchronize()  # any stream may read it from now on
+        _PEAK_TABLES[key] = t
+    return t
+
+
+def _luma_weights(weights):
+    """None (the library's 0.299, 0.587, 0.114) or three floats -> what the C entries take."""
+    if weights is None:
+        return None
+    w = np.asarray(weights, np.float32).ravel()
+    if w.size != 3:
+        raise ValueError(f"weights must be three values (R, G, B); got {weights!r}")
+    return (ctypes.c_float * 3)(*w.tolist())
+
+
+def _peak_table_arg(table, b, grid, like):
+    _require_cuda(table, "table")
+    need = int(L.lib().rti_peak_table_bytes(b, int(grid)))
+    if need <= 0:
+        raise ValueError(f"grid must lie in [4, 16]; got {grid}")
+    if table.dtype != torch.uint8 or table.numel() != need or not table.is_contiguous() or table.device != like.device:
+        raise ValueError(f"table must be peak_table(basis, grid, device): {need} uint8 on {like.device}; got "
+                         f"{table.dtype} {tuple(table.shape)} on {table.device}")
+    return _vp(table)
+
+
+def hsh_normals_into(coef, table, normals, kind=None, peak=None, *, basis="hsh16", layout="pixel",
+                     normal_layout="pixel", grid=10, weights=None):
+    """Launch ``rti_hsh_normals`` on preallocated tensors (no allocation, graph-capturable).
+
+    coef: CUDA fp32, one map [P, k] (layout="pixel") or [k, P] ("planar"), or three [3, P, k] / [3, k, P], any
+    spatial shape in place of P; contiguous, or three contiguous maps a constant stride apart (a [3, ...] view).
+    table: ``peak_table(basis, grid, device)``.  normals: fp32 with 3 values per pixel, [P, 3] or [3, P]; kind:
+    uint8 [P] or None; peak: fp32 [P] or None.  P is normals' pixel count."""
+    b = _hsh8_basis(basis)
+    k = _HSH8_TERMS[b]
+    _require_cuda(coef, "coef")
+    _require_cuda(normals, "normals")
+    P = normals.numel() // 3
+    if coef.dtype != torch.float32 or P < 1 or coef.numel() not in (P * k, 3 * P * k):
+        raise ValueError(f"coef must be float32 with {k} or 3·{k} terms for each of normals' {P} pixels; got "
+                         f"{coef.dtype} {tuple(coef.shape)}")
+    C = coef.numel() // (P * k)
+    if coef.is_contiguous():
+        stride = 0
+    elif C == 3 and coef.shape[0] == 3 and coef[0].is_contiguous() and coef.stride(0) >= P * k:
+        stride = coef.stride(0)
+    else:
+        raise ValueError("coef must be contiguous, or three contiguous maps [3, ...] a constant stride apart")
+    st = L.lib().rti_hsh_normals(_vp(coef), b, _layout_id(layout), C, stride, P, _luma_weights(weights), int(grid),
+                                 _peak_table_arg(table, b, grid, coef),
+                                 _map_out(normals, "normals", torch.float32, 3 * P, coef),
+                                 _normal_layout_id(normal_layout),
+                                 None if kind is None else _map_out(kind, "kind", torch.uint8, P, coef),
+                                 None if peak is None else _map_out(peak, "peak", torch.float32, P, coef),
+                                 _stream_of(coef))
+    L.check(st, "rti_hsh_normals")
+    return normals
+
+
+def hsh8_normals_into(coef8, qparams, table, normals, kind=None, peak=None, *, basis="hsh16", normal_layout="pixel",
+                      grid=10, weights=None):
+    """Launch ``rti_hsh8_normals`` on preallocated tensors (no allocation, graph-capturable).
+
+    coef8: contiguous CUDA uint8 [P, 3, k], any spatial shape in place of P; qparams: CUDA fp32 [2k]; the rest as
+    ``hsh_normals_into``."""
+    b = _hsh8_basis(basis)
+    k = _HSH8_TERMS[b]
+    _require_cuda(coef8, "coef8")
+    if coef8.dtype != torch.uint8 or not coef8.is_contiguous() or coef8.numel() == 0 or coef8.numel() % (3 * k):
+        raise ValueError(f"coef8 must be a contiguous uint8 map of {3 * k} bytes per pixel; got {coef8.dtype} "
+                         f"{tuple(coef8.shape)}")
+    P = coef8.numel() // (3 * k)
+    st = L.lib().rti_hsh8_normals(_vp(coef8), b, P, _hsh_qparams_dev(qparams, k, coef8), _luma_weights(weights),
+                                  int(grid), _peak_table_arg(table, b, grid, coef8),
+                                  _map_out(normals, "normals", torch.float32, 3 * P, coef8),
+                                  _normal_layout_id(normal_layout),
+                                  None if kind is None else _map_out(kind, "kind", torch.uint8, P, coef8),
+                                  None if peak is None else _map_out(peak, "peak", torch.float32, P, coef8),
+                                  _stream_of(coef8))
+    L.check(st, "rti_hsh8_normals")
+    return normals
+
+
+def _normal_outputs(spatial, nl, return_kind, return_peak, device):
+    P = int(np.prod(spatial))
+    n = _coef_empty(1, P, 3, nl, torch.float32, device)
+    kind = torch.empty((1, P), dtype=torch.uint8, device=device) if return_kind else None
+    peak = torch.empty((1, P), dtype=torch.float32, device=device) if return_peak else None
+    return n, kind, peak
+
+
+def _normal_results(n, kind, peak, spatial, nl):
+    out = (_unflatten(n, spatial, False, nl),) + tuple(_unflatten(t, spatial, False) for t in (kind, peak)
+                                                       if t is not None)
+    return out if len(out) > 1 else out[0]
+
+
+def hsh_normals(coef, basis="hsh16", *, layout="pixel", normal_layout="pixel", grid=10, weights=None,
+                return_kind=False, return_peak=False):
+    """Per-pixel surface normals of HSH maps on the GPU (``rti_hsh_normals``): the light direction at which each
+    pixel's fitted function peaks, searched on a grid of directions (i/grid, j/grid) inside the unit disc and
+    refined by one parabolic step.  Each grid value is ``relight``'s float32 value there bit for bit.
+
+    coef: CUDA fp32; one map [H, W, k] / [P, k], or an RGB fit [3, H, W, k] / [3, P, k], whose luminance map
+    (weights, default 0.299, 0.587, 0.114) is searched; with layout="planar" [k, H, W] / [k, P] and
+    [3, k, H, W] / [3, k, P].  A pixel-major 3-D tensor whose first dimension is 3 is read as [3, P, k]: pass a
+    single map of three rows as [P, k].  grid in [4, 16].  Returns what ``normals`` returns: fp32 unit normals
+    [H, W, 3] (or [3, H, W]); with return_kind also uint8 [H, W] (0 peak inside the unit disc, 1 outside it and
+    scaled onto its edge, 2 a flat function: (0, 0, 1), 4 non-finite: NaN); with return_peak also fp32 [H, W], the
+    grid maximum (an albedo proxy)."""
+    _require_cuda(coef, "coef")
+    b = _hsh8_basis(basis)
+    k = _HSH8_TERMS[b]
+    cl, nl = _layout_id(layout), _normal_layout_id(normal_layout)
+    if coef.dtype != torch.float32:
+        raise ValueError("coef must be float32")
+    if cl == L.RTI_COEF_PIXEL_MAJOR:
+        rgb = coef.dim() == 4 or (coef.dim() == 3 and coef.shape[0] == 3)
+    else:
+        rgb = coef.dim() == 4 or (coef.dim() == 3 and coef.shape[0] == 3 and coef.shape[1] == k)
+    if coef.dim() < 2 or coef.dim() > 4 or (rgb and coef.shape[0] != 3):
+        raise ValueError(f"coef must be one HSH map or three, [3, ...]; got {tuple(coef.shape)}")
+    spatial = _coef_spatial(coef[0] if rgb else coef, k, cl)
+    n, kind, peak = _normal_outputs(spatial, nl, return_kind, return_peak, coef.device)
+    hsh_normals_into(coef.contiguous(), peak_table(b, grid, coef.device), n, kind, peak, basis=b, layout=cl,
+                     normal_layout=nl, grid=grid, weights=weights)
+    return _normal_results(n, kind, peak, spatial, nl)
+
+
+def hsh8_normals(q, *, normal_layout="pixel", grid=10, weights=None, return_kind=False, return_peak=False):
+    """Per-pixel surface normals of a quantised RGB HSH map on the GPU (``rti_hsh8_normals``), from the bytes:
+    ``hsh_normals(dequantise_hsh(q), q.basis, ...)`` bit for bit, without the fp32 maps.
+
+    q: a ``QuantisedHSH`` on the GPU.  Returns what ``hsh_normals`` returns."""
+    if not isinstance(q, QuantisedHSH):
+        raise ValueError(f"q must be a QuantisedHSH (quantise_hsh, or read_rti(path, quantised=True)); got "
+                         f"{type(q).__name__}")
+    _require_cuda(q.coef, "q.coef")
+    nl = _normal_layout_id(normal_layout)
+    n, kind, peak = _normal_outputs(q.shape, nl, return_kind, return_peak, q.device)
+    hsh8_normals_into(q.coef, q.qparams, peak_table(q._basis, grid, q.device), n, kind, peak, basis=q._basis,
+                      normal_layout=nl, grid=grid, weights=weights)
+    return _normal_results(n, kind, peak, q.shape, nl)
+
+
 # ---- light operators (RBF, fused PTM/HSH fit + evaluation) ----------------------------------
 
 def _query(qu, qv):

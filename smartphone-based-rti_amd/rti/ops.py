@@ -1,7 +1,7 @@
 """PyTorch custom ops over the C ABI: ``torch.ops.rti.fit_shared`` / ``fit_shared_residual`` /
 ``fit_robust`` / ``fit_accumulate`` / ``fit_accum_solve`` / ``fit_residual`` / ``relight`` / ``ptm_normals`` /
 ``relight_enhanced`` / ``map_unsharp`` / ``shade_normals`` / ``lrgb_from_rgb`` / ``relight_lrgb`` /
-``lrgb_quantise`` / ``relight_lrgb8`` / ``hsh_quantise`` / ``relight_hsh8``.
+``lrgb_quantise`` / ``relight_lrgb8`` / ``hsh_quantise`` / ``relight_hsh8`` / ``hsh_normals`` / ``hsh8_normals``.
 
 They let the fit and relight kernels sit inside torch programs (and
 ``torch.library`` fake-tensor tracing) while the compute stays in librti's
@@ -466,3 +466,60 @@ def relight_hsh8(coef8: torch.Tensor, qparams: torch.Tensor, luv: torch.Tensor,
 @relight_hsh8.register_fake
 def _(coef8, qparams, luv, out_dtype=torch.float32):
     return coef8.new_empty((luv.shape[0], coef8.shape[0], 3), dtype=out_dtype)
+
+
+def _normal_triple(like, P, normals_planar):
+    """(normals, kind, peak) for P pixels on ``like``'s device."""
+    return (like.new_empty((3, P) if normals_planar else (P, 3), dtype=torch.float32),
+            like.new_empty((P,), dtype=torch.uint8), like.new_empty((P,), dtype=torch.float32))
+
+
+def _hsh_map_pixels(coef, k, planar):
+    """P of one HSH map [P, k] / [k, P] or of three [3, P, k] / [3, k, P]."""
+    if k not in (9, 16):
+        raise NotImplementedError(f"HSH normals are HSH-9 and HSH-16 only; got k = {k}")
+    if coef.dim() not in (2, 3) or (coef.dim() == 3 and coef.shape[0] != 3) or coef.shape[-2 if planar else -1] != k:
+        want = f"[{k}, P] or [3, {k}, P]" if planar else f"[P, {k}] or [3, P, {k}]"
+        raise ValueError(f"coef must be {want}; got {tuple(coef.shape)}")
+    return coef.shape[-1 if planar else -2]
+
+
+@torch.library.custom_op("rti::hsh_normals", mutates_args=())
+def hsh_normals(coef: torch.Tensor, k: int = 16, planar: bool = False, normals_planar: bool = False, grid: int = 10,
+                weights: Optional[Sequence[float]] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Surface normals of HSH maps by peak search (``rti_hsh_normals``).  coef CUDA fp32 [P, k] or [3, P, k] (or
+    [k, P] / [3, k, P] if planar), k = 9 or 16, grid in [4, 16], weights None (0.299, 0.587, 0.114) or 3 values ->
+    ``(normals, kind, peak)``: normals fp32 [P, 3] (or [3, P] if normals_planar), kind uint8 [P], peak fp32 [P]."""
+    api._require_cuda(coef, "coef")
+    P = _hsh_map_pixels(coef, k, planar)
+    normals, kind, peak = _normal_triple(coef, P, normals_planar)
+    api.hsh_normals_into(coef.contiguous(), api.peak_table(f"hsh{k}", grid, coef.device), normals, kind, peak,
+                         basis=f"hsh{k}", layout="planar" if planar else "pixel",
+                         normal_layout="planar" if normals_planar else "pixel", grid=grid, weights=weights)
+    return normals, kind, peak
+
+
+@hsh_normals.register_fake
+def _(coef, k=16, planar=False, normals_planar=False, grid=10, weights=None):
+    return _normal_triple(coef, coef.shape[-1 if planar else -2], normals_planar)
+
+
+@torch.library.custom_op("rti::hsh8_normals", mutates_args=())
+def hsh8_normals(coef8: torch.Tensor, qparams: torch.Tensor, normals_planar: bool = False, grid: int = 10,
+                 weights: Optional[Sequence[float]] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Surface normals of a quantised RGB HSH map by peak search (``rti_hsh8_normals``).  coef8 CUDA uint8
+    [P, 3, k] with k = 9 or 16, qparams fp32 [2k] -> ``(normals, kind, peak)`` as ``hsh_normals``."""
+    api._require_cuda(coef8, "coef8")
+    if coef8.dim() != 3 or coef8.shape[1] != 3 or coef8.shape[2] not in (9, 16):
+        raise ValueError(f"coef8 must be [P, 3, 9] or [P, 3, 16]; got {tuple(coef8.shape)}")
+    P, basis = coef8.shape[0], f"hsh{coef8.shape[2]}"
+    normals, kind, peak = _normal_triple(coef8, P, normals_planar)
+    api.hsh8_normals_into(coef8.contiguous(), qparams.contiguous(), api.peak_table(basis, grid, coef8.device), normals,
+                          kind, peak, basis=basis, normal_layout="planar" if normals_planar else "pixel", grid=grid,
+                          weights=weights)
+    return normals, kind, peak
+
+
+@hsh8_normals.register_fake
+def _(coef8, qparams, normals_planar=False, grid=10, weights=None):
+    return _normal_triple(coef8, coef8.shape[0], normals_planar)
