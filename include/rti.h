@@ -799,6 +799,66 @@ int     rti_hsh8_normals(const uint8_t* coef8, int basis, int64_t P, const float
                          float* normals, int normal_layout, uint8_t* kind /* NULL ok */, float* peak /* NULL ok */,
                          rti_stream_t stream);
 
+/* ---- device: 8-bit RGB PTMs, the PTM_FORMAT_RGB payload (rti_rgb8.hip) ---------------------------
+ * A quantised RGB PTM ("RGB8") is the three coefficient blocks of a PTM_FORMAT_RGB payload and its header values:
+ *   coef8:   uint8 [3][p][6]: block R, then G, then B, each the bytes a0..a5 of every pixel (18 bytes per pixel);
+ *   qparams: device fp64 [12]: scale[0..5], bias[0..5] (integral values), shared by the three channels as the file
+ *            header shares them.
+ * Rows top first, as every map of the project (a file stores them bottom first: the flip is the host's).  The
+ * arithmetic is that of rti/io.py (write_ptm(format="rgb"), _ptm_quantise, read_ptm): fp64 from the
+ * fp32 inputs unless an fp32 operation is named, no contraction, each expression left to right as written.
+ * rti_rgb8_qparams_workspace: bytes of device scratch rti_rgb8_qparams needs for P pixels (0 for P < 1); monotone
+ *   in P and at most 36864 (12 floats for each of at most 768 workgroups).
+ * rti_rgb8_qparams: coef: device fp32, three PTM-6 maps as rti_fit_shared writes them with C = 3: [c][p][6]
+ *   (RTI_COEF_PIXEL_MAJOR) or [c][6][p] (RTI_COEF_PLANAR), coef_channel_stride in elements, 0 = dense = 6·P.  One
+ *   pass finds lo_j and hi_j, the smallest and largest finite value of coefficient plane j over the three channels
+ *   (exact fp32 values; min and max are order-independent, so the result does not depend on the reduction tree; no
+ *   atomics); then
+ *     scale_j = ((double)hi_j − (double)lo_j)/255.0 if plane j has a finite value and hi_j > lo_j, else 1
+ *     bias_j  = clip(rint(−(double)lo_j/scale_j), 0, 255) if plane j has a finite value, else 0
+ *   workspace: 4-byte aligned, need not be initialised: the entry reads only what it wrote.  Two launches.
+ *   72 bytes in per pixel.
+ * rti_rgb8_quantise: raw = clip(rint((double)x/scale_j + bias_j), 0, 255); a NaN writes bias_j, ±inf saturates.
+ *   72 bytes in and 18 out per pixel.
+ * rti_relight_rgb8: a_cj = (float)(((double)raw_cj − bias_j)·scale_j), the fp32 map read_ptm builds.  (A workgroup
+ *   forms the 256 possible values of each plane once, in exactly this arithmetic, and a pixel looks its 18 up: the
+ *   same fp32 values.)  Then per channel and direction rti_relight's F32 path: the same basis_eval<float> of
+ *   ((float)lu, (float)lv) and the same chain acc = a_0·b_0, acc = fmaf(a_j, b_j, acc) for j = 1..5, converted once
+ *   (F32; I32 / U8 as rti_relight).  out[e][p][c], RGB interleaved like rti_relight_lrgb's and rti_relight_hsh8's.
+ *   Channel c of the image equals rti_relight's of dequantised map c bit for bit.  A NaN coefficient was stored as
+ *   bias_j and renders as a finite 0 term: that is what the format does.  The bytes are read once for all E
+ *   directions of a launch (the kernel loops over them): 18 bytes in and 3·sizeof(out) per direction out per pixel.
+ * rti_rgb8_normals: luminance in fp32 on the dequantised values, l_j = (wR·r_j + wG·g_j) + wB·b_j: two products and
+ *   two sums, each rounded, no FMA.  w: three fp32 weights on the HOST, NULL = (0.299f, 0.587f, 0.114f), as
+ *   rti_hsh_normals takes them.  Then rti_ptm_normals' per-pixel function on the F32 coefficients l_0..l_5 (fp64
+ *   from the fp32 values; kinds 0 / 1 / 2 / 4; peak): normals, kind and peak equal rti_ptm_normals' of that fp32
+ *   luminance map bit for bit.  The 18 dequantised values of a pixel are finite whenever qparams is, so kind 4
+ *   occurs only if the weighted sum itself overflows fp32: a map made by rti_rgb8_quantise or read from a file,
+ *   with weights of ordinary size, never gives it.  normals: device fp32, normal_layout [p][3] or [3][p]; kind:
+ *   NULL or device uint8 [P]; peak: NULL or device fp32 [P].  One launch; 18 bytes in and 12 (+ 1 + 4) out per
+ *   pixel.
+ * All: device pointers except w, stream-ordered, no allocation, no synchronisation, capturable in a hipGraph.
+ * Every argument check answers before any HIP call.  RTI_ERR_BAD_ARG: a null pointer (kind, peak and w may be null);
+ * P < 1 (or E < 1); a bad coefficient or normal layout; a channel stride below dense; a non-finite weight; a
+ * workspace off 4 bytes; qparams off 8 bytes.  RTI_ERR_UNSUPPORTED: an out_dtype other than F32 / I32 / U8.
+ * The vector path (one lane = 4 pixels; a lane's 24 bytes of a block as three 8-byte loads or six dword stores)
+ * needs P % 4 == 0 (the three blocks are then 24·(P/4) bytes apart, so one alignment covers them), the fp32 maps
+ * 16-byte aligned with a channel stride that is a multiple of 4, coef8 8-byte aligned, out aligned as
+ * rti_relight_lrgb requires (16 bytes; U8: 4) and normals / kind / peak as rti_ptm_normals requires (16 / 4 / 16);
+ * anything else, and the last partial 256-pixel chunk, runs one pixel per lane with the same arithmetic and bits.
+ * Not built: planar or strided coef8, diffuse gain or specular rendering from the bytes, a one-pass relight of fp32
+ * RGB maps. */
+int64_t rti_rgb8_qparams_workspace(int64_t P);
+int rti_rgb8_qparams(const float* coef, int coef_layout, int64_t coef_channel_stride, int64_t P,
+                     void* workspace, double* qparams, rti_stream_t stream);
+int rti_rgb8_quantise(const float* coef, int coef_layout, int64_t coef_channel_stride, int64_t P,
+                      const double* qparams, uint8_t* coef8, rti_stream_t stream);
+int rti_relight_rgb8(const uint8_t* coef8, int64_t P, const double* qparams,
+                     const double* luv, int E, void* out, int out_dtype, rti_stream_t stream);
+int rti_rgb8_normals(const uint8_t* coef8, int64_t P, const double* qparams, const float* w /* HOST, NULL ok */,
+                     float* normals, int normal_layout, uint8_t* kind /* NULL ok */, float* peak /* NULL ok */,
+                     rti_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,549 @@
+// rti_rgb8.hip -- 8-bit RGB PTMs (gfx950): the payload of a PTM_FORMAT_RGB file on the device.
+//
+//     rti_rgb8_qparams    one pass over three fp32 PTM-6 maps -> the file's six scales and six biases
+//     rti_rgb8_quantise   the maps + those 12 doubles -> three blocks of 6 bytes per pixel, R then G then B
+//     rti_relight_rgb8    the 18 bytes + scales and biases -> E interleaved RGB images
+//     rti_rgb8_normals    the 18 bytes -> rti_ptm_normals of their fp32 luminance map
+//
+// The quantiser's arithmetic is rti/io.py's (write_ptm(format="rgb"), _ptm_quantise), in fp64 from the fp32 maps with
+// FP contraction off, so the bytes equal the host's.  A dequantised coefficient is the fp32 value read_ptm builds,
+// (float)(((double)raw − bias_j)·scale_j); the image is rti_relight's F32 path of those values (the same
+// basis_eval<float>, the same FMA chain, cvt_out) and the normals are rti_ptm_normals' per-pixel function
+// (rti_ptm_px.h) of their fp32 luminance, so both equal what the fp32 entries give for the dequantised maps bit for
+// bit.
+//
+// Dequantisation is not per-pixel arithmetic: a byte of plane j can only become one of 256 fp32 values, so every
+// workgroup of the two reading kernels first fills six 256-entry fp32 tables in LDS (6 KiB; each of its 256 lanes
+// forms entry t = threadIdx.x of the six tables in fp64 and rounds it once) and a pixel then costs 18 LDS reads and
+// no fp64 operation.  The table holds the very (float) values the expression gives, so nothing downstream can tell.
+//
+// All kernels keep rti_relight's lane map (a lane owns 4 consecutive pixels, a wave 256, a block 1024) and
+// rti_lrgb_px.h's loads of the fp32 maps.  A lane's 24 bytes of a channel block are contiguous: they are read as
+// three 8-byte loads per block and written as six dwords.  The extremes are order-independent (min and max of finite
+// values), so the reduction tree does not show in the result: a lane folds its pixels into 12 floats, a wave folds
+// its lanes with shuffles, a workgroup its waves through LDS, and every workgroup of the grid writes its 12 partials
+// to the workspace; a one-workgroup tail folds those and forms the 12 doubles.  No atomics, and no workspace word is
+// read that this call did not write.
+//
+// A launch whose P is no multiple of 4 or whose pointers are not aligned for the vector accesses, and the last
+// partial wave of any launch, take one pixel per lane through the same per-pixel functions.
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <cmath>
+#include <cstdint>
+
+#include "rti_basis.h"
+#include "rti_convert.h"
+#include "rti_hsh_px.h"
+#include "rti_lrgb_px.h"
+#include "rti_ptm_px.h"
+#include "rti_stack.h"
+
+namespace rti {
+namespace {
+
+using namespace lrgb_px;  // K = 6, the wave loads of fp32 maps, the staged row stores
+using hsh_px::dot_k;      // rti_relight's fp32 chain
+
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int NQ = 2 * K;            // a partial: lo[6], hi[6]; qparams: scale[6], bias[6]
+constexpr int QP_MAX_BLOCKS = 768;   // the extremes' grid: 3 workgroups per CU of 256, each striding over chunks
+
+inline int64_t qparams_blocks(int64_t P) {
+  const int64_t chunks = (P + 1023) / 1024;
+  return chunks < QP_MAX_BLOCKS ? chunks : QP_MAX_BLOCKS;
+}
+
+// ---- extremes ----------------------------------------------------------------------------------------------------
+// q[j], q[6 + j]: min and max of the finite values of plane j in the three channels.  A plane without a finite
+// value keeps lo = +inf > hi = -inf.
+
+__device__ __forceinline__ void ext_init(float (&q)[NQ]) {
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    q[j] = INFINITY;
+    q[K + j] = -INFINITY;
+  }
+}
+
+__device__ __forceinline__ float ext_fold(int i, float a, float b) { return i < K ? fminf(a, b) : fmaxf(a, b); }
+
+__device__ __forceinline__ void ext_pixel(float (&q)[NQ], const float (&m)[K]) {
+#pragma unroll
+  for (int j = 0; j < K; ++j)
+    if (fabsf(m[j]) <= FLT_MAX) {  // false for NaN
+      q[j] = fminf(q[j], m[j]);
+      q[K + j] = fmaxf(q[K + j], m[j]);
+    }
+}
+
+// the workgroup's 256 lanes -> thread i < NQ returns value i
+__device__ __forceinline__ float ext_block_fold(float (&q)[NQ], float (*part)[NQ]) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < NQ; ++i) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) q[i] = ext_fold(i, q[i], __shfl_xor(q[i], m, 64));
+    if (lane == 0) part[wave][i] = q[i];
+  }
+  __syncthreads();
+  const int i = threadIdx.x < NQ ? threadIdx.x : 0;
+  return ext_fold(i, ext_fold(i, part[0][i], part[1][i]), ext_fold(i, part[2][i], part[3][i]));
+}
+
+template <int CL>
+__global__ void __launch_bounds__(256)
+rgb_extremes_k(const float* __restrict__ coef, int64_t cs, int64_t P, int vec, float* __restrict__ partial) {
+  constexpr int SLAB = slab_v4(CL == RTI_COEF_PIXEL_MAJOR ? K : 0, 0);
+  __shared__ floatx4 slabs[4 * SLAB];
+  __shared__ float part[4][NQ];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  floatx4* slab = slabs + wave * SLAB;
+  float q[NQ];
+  ext_init(q);
+  const int64_t chunks = (P + 1023) / 1024;
+  for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
+    const int64_t wave_px = (c * 4 + wave) * 256;
+    if (wave_px >= P) continue;       // wave-uniform
+    if (vec && wave_px + 256 <= P) {  // wave-uniform
+#pragma unroll 1
+      for (int ch = 0; ch < 3; ++ch) {
+        float m[4][K];
+        load_wave<K, CL>(coef + ch * cs, P, wave_px, lane, slab, m);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) ext_pixel(q, m[v]);
+      }
+    } else {
+      for (int j = 0; j < 4; ++j) {
+        const int64_t p = wave_px + 64 * j + lane;
+        if (p >= P) break;
+#pragma unroll 1
+        for (int ch = 0; ch < 3; ++ch) {
+          float m[K];
+          load_pixel<K, CL>(coef + ch * cs, P, p, m);
+          ext_pixel(q, m);
+        }
+      }
+    }
+  }
+  const float r = ext_block_fold(q, part);
+  if (threadIdx.x < NQ) partial[(int64_t)blockIdx.x * NQ + threadIdx.x] = r;
+}
+
+// n partials -> qparams; one workgroup
+__global__ void __launch_bounds__(256)
+rgb_qparams_k(const float* __restrict__ partial, int n, double* __restrict__ qparams) {
+#pragma clang fp contract(off)
+  __shared__ float part[4][NQ];
+  __shared__ float fin[NQ];
+  float q[NQ];
+  ext_init(q);
+  for (int b = threadIdx.x; b < n; b += 256)
+#pragma unroll
+    for (int i = 0; i < NQ; ++i) q[i] = ext_fold(i, q[i], partial[(int64_t)b * NQ + i]);
+  const float r = ext_block_fold(q, part);
+  if (threadIdx.x < NQ) fin[threadIdx.x] = r;
+  __syncthreads();
+  if (threadIdx.x < K) {
+    const int j = threadIdx.x;
+    const bool has = fin[j] <= fin[K + j];  // the plane has a finite value
+    const double LO = (double)fin[j], HI = (double)fin[K + j];
+    const double scale = has && HI > LO ? (HI - LO) / 255.0 : 1.0;
+    double bias = 0.0;
+    if (has) {
+      const double b = rint(-LO / scale);
+      bias = b > 0.0 ? (b < 255.0 ? b : 255.0) : 0.0;  // -0.0 -> 0.0
+    }
+    qparams[j] = scale;
+    qparams[K + j] = bias;
+  }
+}
+
+// ---- per-pixel quantisation (fp64, no contraction) ---------------------------------------------------------------
+
+struct QParams {
+  double scale[K], bias[K];
+};
+
+__device__ __forceinline__ QParams load_qparams(const double* __restrict__ qparams) {
+  QParams q;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    q.scale[j] = qparams[j];
+    q.bias[j] = qparams[K + j];
+  }
+  return q;
+}
+
+// rint(t) clipped to a byte; NaN -> 0
+__device__ __forceinline__ uint8_t byte_of(double t) {
+  const double r = rint(t);
+  return (uint8_t)(int)(r > 0.0 ? (r < 255.0 ? r : 255.0) : 0.0);
+}
+
+// six fp32 coefficients of one channel of a pixel -> their bytes (rti/io.py: _ptm_quantise)
+__device__ __forceinline__ void quantise_px(const float (&m)[K], const QParams& q, uint8_t (&cb)[K]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const double x = (double)m[j];
+    cb[j] = x != x ? (uint8_t)(int)q.bias[j] : byte_of(x / q.scale[j] + q.bias[j]);
+  }
+}
+
+// NB bytes (a multiple of 4) of a lane as dwords
+template <int NB>
+__device__ __forceinline__ void store_dwords(uint8_t* __restrict__ dst, const uint8_t* f) {
+  uint32_t* o4 = reinterpret_cast<uint32_t*>(dst);
+#pragma unroll
+  for (int w = 0; w < NB / 4; ++w)
+    o4[w] = (uint32_t)f[4 * w] | ((uint32_t)f[4 * w + 1] << 8) | ((uint32_t)f[4 * w + 2] << 16) |
+            ((uint32_t)f[4 * w + 3] << 24);
+}
+
+// ---- dequantisation: six 256-entry tables per workgroup ---------------------------------------------------------
+// tab[j][t] = (float)(((double)t − bias_j)·scale_j), the fp32 value read_ptm gives byte t of plane j.  Every lane of
+// the workgroup's 256 forms entry t = threadIdx.x of the six tables; the caller synchronises the workgroup.
+
+constexpr int TAB = 256;
+
+__device__ __forceinline__ void fill_tables(const double* __restrict__ qparams, float* __restrict__ tab) {
+#pragma clang fp contract(off)
+  const double t = (double)threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < K; ++j) tab[j * TAB + threadIdx.x] = (float)((t - qparams[K + j]) * qparams[j]);
+}
+
+// the 18 bytes of 4 consecutive pixels: three 8-byte loads from each of the three blocks
+struct Bytes4 {
+  union {
+    u32x2 v[3];
+    uint8_t b[4][K];
+  } c[3];
+};
+
+__device__ __forceinline__ void load_bytes4(const uint8_t* __restrict__ coef8, int64_t P, int64_t p0, Bytes4& r) {
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const u32x2* s = reinterpret_cast<const u32x2*>(coef8 + ((int64_t)ch * P + p0) * K);
+#pragma unroll
+    for (int w = 0; w < 3; ++w) r.c[ch].v[w] = s[w];
+  }
+}
+
+__device__ __forceinline__ void load_bytes1(const uint8_t* __restrict__ coef8, int64_t P, int64_t p, uint8_t (&b)[3][K]) {
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch)
+#pragma unroll
+    for (int j = 0; j < K; ++j) b[ch][j] = coef8[((int64_t)ch * P + p) * K + j];
+}
+
+__device__ __forceinline__ void dequantise_px(const uint8_t (&b)[K], const float* __restrict__ tab, float (&a)[K]) {
+#pragma unroll
+  for (int j = 0; j < K; ++j) a[j] = tab[j * TAB + b[j]];
+}
+
+// three channels of a pixel -> the fp32 luminance map: two products and two sums, each rounded
+__device__ __forceinline__ void luminance(const float (&c)[3][K], float wr, float wg, float wb, float (&l)[K]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const float rg = wr * c[0][j] + wg * c[1][j];
+    l[j] = rg + wb * c[2][j];
+  }
+}
+
+// ---- kernels ------------------------------------------------------------------------------------------------------
+// All: a wave owns pixels [wave_px, wave_px + 256), as rti_lrgb8.hip's kernels.
+
+template <int CL>
+__global__ void __launch_bounds__(256)
+rgb_quantise_k(const float* __restrict__ coef, int64_t cs, int64_t P, int vec, const double* __restrict__ qparams,
+               uint8_t* __restrict__ coef8) {
+  constexpr int SLAB = slab_v4(CL == RTI_COEF_PIXEL_MAJOR ? K : 0, 0);
+  __shared__ floatx4 slabs[4 * SLAB];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
+  if (wave_px >= P) return;
+  const QParams q = load_qparams(qparams);
+  if (vec && wave_px + 256 <= P) {  // wave-uniform
+    const int64_t p0 = wave_px + 4 * lane;
+#pragma unroll 1
+    for (int ch = 0; ch < 3; ++ch) {
+      float m[4][K];
+      load_wave<K, CL>(coef + ch * cs, P, wave_px, lane, slabs + wave * SLAB, m);
+      uint8_t cb[4][K];
+#pragma unroll
+      for (int v = 0; v < 4; ++v) quantise_px(m[v], q, cb[v]);
+      store_dwords<4 * K>(coef8 + ((int64_t)ch * P + p0) * K, &cb[0][0]);
+    }
+    return;
+  }
+  for (int j = 0; j < 4; ++j) {
+    const int64_t p = wave_px + 64 * j + lane;
+    if (p >= P) break;
+#pragma unroll 1
+    for (int ch = 0; ch < 3; ++ch) {
+      float m[K];
+      load_pixel<K, CL>(coef + ch * cs, P, p, m);
+      uint8_t cb[K];
+      quantise_px(m, q, cb);
+#pragma unroll
+      for (int i = 0; i < K; ++i) coef8[((int64_t)ch * P + p) * K + i] = cb[i];
+    }
+  }
+}
+
+// one pixel's three channels at the basis row b, converted once: rti_relight's F32 path per channel
+template <typename TO>
+__device__ __forceinline__ void rgb_px(const float (&a)[3][K], const float (&b)[K], TO (&o)[3]) {
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) o[ch] = cvt_out<TO>(dot_k<K>(a[ch], b));
+}
+
+template <typename TO>
+__global__ void __launch_bounds__(256)
+relight_rgb8_k(const uint8_t* __restrict__ coef8, int64_t P, int vec, const double* __restrict__ qparams,
+               const double* __restrict__ luv, int E, TO* __restrict__ out) {
+  constexpr bool STAGE_OUT = sizeof(TO) == 4;  // fp32 / int32: 48 B per lane through the slab
+  constexpr int SLAB = slab_v4(0, STAGE_OUT ? 3 : 0);
+  __shared__ floatx4 slabs[4 * SLAB];
+  __shared__ float tab[K * TAB];
+  fill_tables(qparams, tab);
+  __syncthreads();  // the one workgroup barrier: waves may leave below
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
+  if (wave_px >= P) return;
+  floatx4* slab = slabs + wave * SLAB;
+  if (vec && wave_px + 256 <= P) {  // wave-uniform
+    Bytes4 r;
+    load_bytes4(coef8, P, wave_px + 4 * lane, r);
+    float a[4][3][K];
+#pragma unroll
+    for (int v = 0; v < 4; ++v)
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) dequantise_px(r.c[ch].b[v], tab, a[v][ch]);
+    for (int e = 0; e < E; ++e) {
+      float b[K];
+      ptm_eval<float>((float)luv[2 * e], (float)luv[2 * e + 1], b);  // basis_eval<float>'s PTM-6 branch
+      TO o[4][3];
+#pragma unroll
+      for (int v = 0; v < 4; ++v) rgb_px<TO>(a[v], b, o[v]);
+      TO* rows = out + ((int64_t)e * P + wave_px) * 3;
+      if constexpr (STAGE_OUT)
+        store_rows_staged<3, TO>(rows, lane, slab, o);
+      else
+        store_dwords<12>(rows + 12 * lane, &o[0][0]);
+    }
+    return;
+  }
+  for (int j = 0; j < 4; ++j) {
+    const int64_t p = wave_px + 64 * j + lane;
+    if (p >= P) break;
+    uint8_t cb[3][K];
+    load_bytes1(coef8, P, p, cb);
+    float a[3][K];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) dequantise_px(cb[ch], tab, a[ch]);
+    for (int e = 0; e < E; ++e) {
+      float b[K];
+      ptm_eval<float>((float)luv[2 * e], (float)luv[2 * e + 1], b);
+      TO o[3];
+      rgb_px<TO>(a, b, o);
+      TO* px = out + ((int64_t)e * P + p) * 3;
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) px[ch] = o[ch];
+    }
+  }
+}
+
+struct Weights {
+  float r, g, b;
+};
+
+// 18 bytes of a pixel -> what rti_ptm_normals writes for its fp32 luminance coefficients
+__device__ __forceinline__ ptm_px::NormalOut normal_px(const float (&c)[3][K], const Weights& w, bool want_peak) {
+  float l[K];
+  luminance(c, w.r, w.g, w.b, l);
+  double a[K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) a[j] = (double)l[j];
+  return ptm_px::normal_of(a, want_peak);
+}
+
+template <int NL>
+__global__ void __launch_bounds__(256)
+rgb8_normals_k(const uint8_t* __restrict__ coef8, int64_t P, int vec, const double* __restrict__ qparams, Weights w,
+               float* __restrict__ normals, uint8_t* __restrict__ kind, float* __restrict__ peak) {
+  constexpr bool STAGE_OUT = NL == RTI_NORMAL_PIXEL_MAJOR;
+  constexpr int SLAB = slab_v4(0, STAGE_OUT ? 3 : 0);
+  __shared__ floatx4 slabs[4 * SLAB];
+  __shared__ float tab[K * TAB];
+  fill_tables(qparams, tab);
+  __syncthreads();  // the one workgroup barrier: waves may leave below
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
+  if (wave_px >= P) return;
+  floatx4* slab = slabs + wave * SLAB;
+  if (vec && wave_px + 256 <= P) {  // wave-uniform
+    const int64_t p0 = wave_px + 4 * lane;
+    Bytes4 r;
+    load_bytes4(coef8, P, p0, r);
+    ptm_px::NormalOut o[4];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      float c[3][K];
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) dequantise_px(r.c[ch].b[v], tab, c[ch]);
+      o[v] = normal_px(c, w, peak != nullptr);
+    }
+    if (kind)
+      *reinterpret_cast<uint32_t*>(kind + p0) = (uint32_t)o[0].kind | ((uint32_t)o[1].kind << 8) |
+                                                ((uint32_t)o[2].kind << 16) | ((uint32_t)o[3].kind << 24);
+    if (peak) *reinterpret_cast<floatx4*>(peak + p0) = floatx4{o[0].peak, o[1].peak, o[2].peak, o[3].peak};
+    if constexpr (STAGE_OUT) {
+      float n[4][3];
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) n[v][i] = o[v].n[i];
+      store_rows_staged<3, float>(normals + wave_px * 3, lane, slab, n);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        *reinterpret_cast<floatx4*>(normals + (int64_t)i * P + p0) = floatx4{o[0].n[i], o[1].n[i], o[2].n[i], o[3].n[i]};
+    }
+    return;
+  }
+  for (int j = 0; j < 4; ++j) {
+    const int64_t p = wave_px + 64 * j + lane;
+    if (p >= P) break;
+    uint8_t cb[3][K];
+    load_bytes1(coef8, P, p, cb);
+    float c[3][K];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) dequantise_px(cb[ch], tab, c[ch]);
+    const ptm_px::NormalOut o = normal_px(c, w, peak != nullptr);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) normals[NL == RTI_NORMAL_PLANAR ? (int64_t)i * P + p : p * 3 + i] = o.n[i];
+    if (kind) kind[p] = o.kind;
+    if (peak) peak[p] = o.peak;
+  }
+}
+
+// ---- launchers and checks -----------------------------------------------------------------------------------------
+
+template <typename TO>
+void launch_relight8(const uint8_t* coef8, int64_t P, int vec, const double* qparams, const double* luv, int E,
+                     void* out, hipStream_t s) {
+  hipLaunchKernelGGL((relight_rgb8_k<TO>), dim3(grid_1d(P, 1024)), dim3(256), 0, s, coef8, P, vec, qparams, luv, E,
+                     static_cast<TO*>(out));
+}
+
+// the checks rti_rgb8_qparams and rti_rgb8_quantise share, in the order include/rti.h lists them
+int check_rgb_maps(const char* entry, int layout, int64_t stride, int64_t P) {
+  if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", entry);
+  if (int st = check_coef_layout(entry, layout)) return st;
+  return check_coef_stride(entry, coef_view(static_cast<const float*>(nullptr), layout, K, P, stride), P, 3);
+}
+
+// 16-byte loads of the three maps: every wave's rows (or plane pieces) of every channel start on a 16-byte boundary
+inline int maps_vec(const float* coef, int64_t cs, int64_t P) {
+  return P % 4 == 0 && aligned_to(coef, 16) && cs % 4 == 0 ? 1 : 0;
+}
+
+}  // namespace
+}  // namespace rti
+
+using namespace rti;
+
+extern "C" int64_t rti_rgb8_qparams_workspace(int64_t P) {
+  return P < 1 ? 0 : qparams_blocks(P) * NQ * (int64_t)sizeof(float);
+}
+
+extern "C" int rti_rgb8_qparams(const float* coef, int coef_layout, int64_t coef_channel_stride, int64_t P,
+                                void* workspace, double* qparams, rti_stream_t stream) {
+  const char* const E = "rti_rgb8_qparams";
+  if (int st = check_pointers(E, {coef, workspace, qparams})) return st;
+  if (int st = check_rgb_maps(E, coef_layout, coef_channel_stride, P)) return st;
+  if (!aligned_to(workspace, 4) || !aligned_to(qparams, 8))
+    return fail(RTI_ERR_BAD_ARG, "%s: workspace must be 4-byte and qparams 8-byte aligned", E);
+  const int64_t cs = coef_channel_stride ? coef_channel_stride : P * K;
+  const int blocks = (int)qparams_blocks(P);
+  const int vec = maps_vec(coef, cs, P);
+  float* partial = static_cast<float*>(workspace);
+  note_launches(2);
+  if (coef_layout == RTI_COEF_PLANAR)
+    hipLaunchKernelGGL((rgb_extremes_k<RTI_COEF_PLANAR>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, coef, cs, P,
+                       vec, partial);
+  else
+    hipLaunchKernelGGL((rgb_extremes_k<RTI_COEF_PIXEL_MAJOR>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, coef,
+                       cs, P, vec, partial);
+  if (int st = check_launch(E)) return st;
+  hipLaunchKernelGGL(rgb_qparams_k, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, blocks, qparams);
+  return check_launch(E);
+}
+
+extern "C" int rti_rgb8_quantise(const float* coef, int coef_layout, int64_t coef_channel_stride, int64_t P,
+                                 const double* qparams, uint8_t* coef8, rti_stream_t stream) {
+  const char* const E = "rti_rgb8_quantise";
+  if (int st = check_pointers(E, {coef, qparams, coef8})) return st;
+  if (int st = check_rgb_maps(E, coef_layout, coef_channel_stride, P)) return st;
+  if (!aligned_to(qparams, 8)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 8-byte aligned", E);
+  const int64_t cs = coef_channel_stride ? coef_channel_stride : P * K;
+  const int vec = maps_vec(coef, cs, P) && aligned_to(coef8, 8) ? 1 : 0;
+  note_launches(1);
+  if (coef_layout == RTI_COEF_PLANAR)
+    hipLaunchKernelGGL((rgb_quantise_k<RTI_COEF_PLANAR>), dim3(grid_1d(P, 1024)), dim3(256), 0, (hipStream_t)stream,
+                       coef, cs, P, vec, qparams, coef8);
+  else
+    hipLaunchKernelGGL((rgb_quantise_k<RTI_COEF_PIXEL_MAJOR>), dim3(grid_1d(P, 1024)), dim3(256), 0,
+                       (hipStream_t)stream, coef, cs, P, vec, qparams, coef8);
+  return check_launch(E);
+}
+
+extern "C" int rti_relight_rgb8(const uint8_t* coef8, int64_t P, const double* qparams, const double* luv, int E_,
+                                void* out, int out_dtype, rti_stream_t stream) {
+  const char* const E = "rti_relight_rgb8";
+  if (int st = check_pointers(E, {coef8, qparams, luv, out})) return st;
+  if (P < 1 || E_ < 1) return fail(RTI_ERR_BAD_ARG, "%s: P and E must be positive", E);
+  if (out_dtype != RTI_F32 && out_dtype != RTI_I32 && out_dtype != RTI_U8)
+    return fail(RTI_ERR_UNSUPPORTED, "%s: out dtype %d", E, out_dtype);
+  if (!aligned_to(qparams, 8)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 8-byte aligned", E);
+  const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // a lane's dword / the wave's 16-byte pieces
+  const int vec = P % 4 == 0 && aligned_to(coef8, 8) && aligned_to(out, ovec) ? 1 : 0;
+  note_launches(1);
+  switch (out_dtype) {
+    case RTI_F32: launch_relight8<float>(coef8, P, vec, qparams, luv, E_, out, (hipStream_t)stream); break;
+    case RTI_I32: launch_relight8<int32_t>(coef8, P, vec, qparams, luv, E_, out, (hipStream_t)stream); break;
+    default: launch_relight8<uint8_t>(coef8, P, vec, qparams, luv, E_, out, (hipStream_t)stream); break;
+  }
+  return check_launch(E);
+}
+
+extern "C" int rti_rgb8_normals(const uint8_t* coef8, int64_t P, const double* qparams, const float* w,
+                                float* normals, int normal_layout, uint8_t* kind, float* peak, rti_stream_t stream) {
+  const char* const E = "rti_rgb8_normals";
+  if (int st = check_pointers(E, {coef8, qparams, normals})) return st;
+  if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", E);
+  if (normal_layout != RTI_NORMAL_PIXEL_MAJOR && normal_layout != RTI_NORMAL_PLANAR)
+    return fail(RTI_ERR_BAD_ARG, "%s: normal layout %d", E, normal_layout);
+  const Weights wt{w ? w[0] : 0.299f, w ? w[1] : 0.587f, w ? w[2] : 0.114f};
+  if (!std::isfinite(wt.r) || !std::isfinite(wt.g) || !std::isfinite(wt.b))
+    return fail(RTI_ERR_BAD_ARG, "%s: non-finite weight", E);
+  if (!aligned_to(qparams, 8)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 8-byte aligned", E);
+  const int vec = P % 4 == 0 && aligned_to(coef8, 8) && aligned_to(normals, 16) && (!kind || aligned_to(kind, 4)) &&
+                          (!peak || aligned_to(peak, 16))
+                      ? 1
+                      : 0;
+  note_launches(1);
+  if (normal_layout == RTI_NORMAL_PLANAR)
+    hipLaunchKernelGGL((rgb8_normals_k<RTI_NORMAL_PLANAR>), dim3(grid_1d(P, 1024)), dim3(256), 0, (hipStream_t)stream,
+                       coef8, P, vec, qparams, wt, normals, kind, peak);
+  else
+    hipLaunchKernelGGL((rgb8_normals_k<RTI_NORMAL_PIXEL_MAJOR>), dim3(grid_1d(P, 1024)), dim3(256), 0,
+                       (hipStream_t)stream, coef8, P, vec, qparams, wt, normals, kind, peak);
+  return check_launch(E);
+}

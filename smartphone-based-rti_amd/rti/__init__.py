@@ -31,6 +31,11 @@ bara96/Smartphone-based-RTI: analysis.py:196-411, interactive_relighting.py:11-3
     n, albedo = rti.hsh8_normals(h, return_peak=True)             # where each pixel's HSH function peaks
     img = rti.shade_normals(rti.normals_unsharp(n, 2.0, 1.5), 0.3, -0.2, albedo=albedo, ks=150, exp=75)
 
+    p = rti.quantise_rgb(rti.fit(Irgb, lu, lv))      # RGB PTM as the 18 bytes per pixel of PTM_FORMAT_RGB
+    rgb = rti.relight_rgb8(p, 0.3, -0.2, out_dtype=torch.uint8)   # one launch, from the bytes
+    n = rti.rgb8_normals(p)                          # normals of the luminance, from the bytes
+    rti.write_ptm("object.ptm", p)                   # and back: rti.read_ptm8("object.ptm")[1].to("cuda")
+
 Compute runs in HIP kernels of librti.so (include/rti.h); importing this
 package does not touch the GPU.
 """
@@ -47,8 +52,10 @@ from .api import (BASES, FitAccumulator, apply_operator, basis_eval, basis_id, b
                   quantise_lrgb, relight_lrgb8, relight_lrgb8_into,
                   QuantisedHSH, dequantise_hsh, hsh_qparams_into, hsh_qparams_workspace, hsh_quantise_into,
                   quantise_hsh, relight_hsh8, relight_hsh8_into,
-                  hsh8_normals, hsh8_normals_into, hsh_normals, hsh_normals_into, peak_grid_points, peak_table)
-from .io import read_ptm, read_rti, write_ptm, write_rti
+                  hsh8_normals, hsh8_normals_into, hsh_normals, hsh_normals_into, peak_grid_points, peak_table,
+                  QuantisedRGB, dequantise_rgb, quantise_rgb, relight_rgb8, relight_rgb8_into, rgb8_normals,
+                  rgb8_normals_into, rgb8_qparams_into, rgb8_qparams_workspace, rgb8_quantise_into)
+from .io import read_ptm, read_ptm8, read_rti, write_ptm, write_rti
 
 __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_into", "fit_chunked",
            "RTIError", "RTILibraryMissing", "apply_operator", "basis_eval", "basis_id", "basis_operator",
@@ -63,7 +70,9 @@ __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_in
            "lrgb_qparams_into", "lrgb_qparams_workspace", "lrgb_quantise_into", "quantise_lrgb", "relight_lrgb8",
            "relight_lrgb8_into", "QuantisedHSH", "dequantise_hsh", "hsh_qparams_into", "hsh_qparams_workspace",
            "hsh_quantise_into", "quantise_hsh", "relight_hsh8", "relight_hsh8_into", "hsh8_normals",
-           "hsh8_normals_into", "hsh_normals", "hsh_normals_into", "peak_grid_points", "peak_table", "read_ptm", "write_ptm",
+           "hsh8_normals_into", "hsh_normals", "hsh_normals_into", "peak_grid_points", "peak_table", "QuantisedRGB",
+           "dequantise_rgb", "quantise_rgb", "relight_rgb8", "relight_rgb8_into", "rgb8_normals", "rgb8_normals_into",
+           "rgb8_qparams_into", "rgb8_qparams_workspace", "rgb8_quantise_into", "read_ptm", "read_ptm8", "write_ptm",
            "read_rti", "write_rti", "library_path", "load"]
 
 __version__ = "0.1.0"

@@ -180,6 +180,12 @@ SIGNATURES = {
                                  _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p]),
     "rti_hsh8_normals": (_c_int, [_c_void_p, _c_int, _c_i64, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p,
                                   _c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "rti_rgb8_qparams_workspace": (_c_i64, [_c_i64]),
+    "rti_rgb8_qparams": (_c_int, [_c_void_p, _c_int, _c_i64, _c_i64, _c_void_p, _c_void_p, _c_void_p]),
+    "rti_rgb8_quantise": (_c_int, [_c_void_p, _c_int, _c_i64, _c_i64, _c_void_p, _c_void_p, _c_void_p]),
+    "rti_relight_rgb8": (_c_int, [_c_void_p, _c_i64, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p]),
+    "rti_rgb8_normals": (_c_int, [_c_void_p, _c_i64, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p,
+                                  _c_void_p]),
 }
 
 _lock = threading.Lock()

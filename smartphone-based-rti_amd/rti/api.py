@@ -1916,6 +1916,242 @@ def hsh8_normals(q, *, normal_layout="pixel", grid=10, weights=None, return_kind
     return _normal_results(n, kind, peak, q.shape, nl)
 
 
+# ---- 8-bit RGB PTMs: the PTM_FORMAT_RGB payload on the device (rti_rgb8.hip) --
+
+class QuantisedRGB:
+    """An 8-bit RGB PTM: the three coefficient blocks of a ``PTM_FORMAT_RGB`` payload and its header values.
+
+    coef: uint8 [3, H, W, 6] or [3, P, 6]: block R, then G, then B, each the bytes a0..a5 per pixel; qparams: fp64
+    [12] = scale[0..5], bias[0..5] (integral), shared by the three channels as the file header shares them.  A
+    coefficient is ``(byte − bias)·scale`` (``dequantise_rgb``).  Rows top first.  Both tensors on one device (the
+    GPU, or the host for ``read_ptm8``); immutable.  ``scale`` / ``bias`` copy qparams to the host: they are the
+    one accessor that synchronises."""
+    __slots__ = ("_coef", "_qparams")
+
+    def __init__(self, coef, qparams):
+        if not (torch.is_tensor(coef) and torch.is_tensor(qparams)):
+            raise ValueError("QuantisedRGB takes two tensors (coef, qparams)")
+        if coef.dtype != torch.uint8 or coef.dim() < 3 or coef.shape[0] != 3 or coef.shape[-1] != 6 \
+                or coef.numel() == 0 or not coef.is_contiguous():
+            raise ValueError(f"coef must be a contiguous uint8 [3, ..., 6] tensor; got {coef.dtype} "
+                             f"{tuple(coef.shape)}")
+        if qparams.dtype != torch.float64 or tuple(qparams.shape) != (12,) or not qparams.is_contiguous():
+            raise ValueError(f"qparams must be a contiguous float64 [12] tensor; got {qparams.dtype} "
+                             f"{tuple(qparams.shape)}")
+        if coef.device != qparams.device:
+            raise ValueError(f"coef and qparams must be on one device; got {coef.device}, {qparams.device}")
+        for name, v in zip(self.__slots__, (coef, qparams)):
+            object.__setattr__(self, name, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("QuantisedRGB is immutable")
+
+    coef = property(lambda self: self._coef)
+    qparams = property(lambda self: self._qparams)
+    shape = property(lambda self: tuple(self._coef.shape[1:-1]), doc="the spatial shape: (H, W) or (P,)")
+    device = property(lambda self: self._coef.device)
+
+    def _host(self):
+        return self._qparams.detach().cpu().numpy()
+
+    scale = property(lambda self: self._host()[:6].copy(), doc="host fp64 [6] (synchronises)")
+    bias = property(lambda self: self._host()[6:].copy(), doc="host fp64 [6], integral values (synchronises)")
+
+    def to(self, device):
+        return QuantisedRGB(self._coef.to(device), self._qparams.to(device))
+
+    def with_file_scales(self):
+        """The map as a .ptm round trip yields it: the same bytes, the scales rounded to the nine significant
+        digits ``write_ptm`` puts in the header.  ``quantise_rgb`` keeps the full fp64 scales the bytes were made
+        with; a file does not, so ``dequantise_rgb`` / ``relight_rgb8`` / ``rgb8_normals`` of this map, not of the
+        fresh one, equal those of the written file to the bit.  Synchronises."""
+        qp = self._host().copy()
+        qp[:6] = [float("%.9g" % x) for x in qp[:6]]
+        return QuantisedRGB(self._coef, torch.as_tensor(qp).to(self.device))
+
+    def __repr__(self):
+        return f"QuantisedRGB(shape={self.shape}, device={self.device})"
+
+
+def _quantised_rgb(q, name="q"):
+    """A QuantisedRGB on the GPU -> P."""
+    if not isinstance(q, QuantisedRGB):
+        raise ValueError(f"{name} must be a QuantisedRGB (quantise_rgb, or read_ptm8(path)); got {type(q).__name__}")
+    _require_cuda(q.coef, f"{name}.coef")
+    return q.coef.numel() // 18
+
+
+def _rgb_maps(coef):
+    """Three contiguous CUDA fp32 PTM-6 maps, [3, ...] -> P."""
+    _require_cuda(coef, "coef")
+    if coef.dtype != torch.float32 or not coef.is_contiguous() or coef.dim() < 2 or coef.shape[0] != 3 \
+            or coef.numel() == 0 or coef.numel() % 18:
+        raise ValueError(f"coef must be three contiguous float32 maps of 6 terms per pixel, [3, ...]; got "
+                         f"{coef.dtype} {tuple(coef.shape)}")
+    return coef.numel() // 18
+
+
+def _rgb8_qparams_dev(qparams, like):
+    _require_cuda(qparams, "qparams")
+    if qparams.dtype != torch.float64 or qparams.numel() != 12 or not qparams.is_contiguous() \
+            or qparams.device != like.device:
+        raise ValueError(f"qparams must be a contiguous float64 [12] tensor on {like.device}; got {qparams.dtype} "
+                         f"{tuple(qparams.shape)} on {qparams.device}")
+    return _vp(qparams)
+
+
+def _rgb8_bytes(coef8):
+    """A contiguous CUDA uint8 map of three blocks of 6 bytes per pixel -> P."""
+    _require_cuda(coef8, "coef8")
+    if coef8.dtype != torch.uint8 or not coef8.is_contiguous() or coef8.numel() == 0 or coef8.numel() % 18:
+        raise ValueError(f"coef8 must be a contiguous uint8 map of three blocks of 6 bytes per pixel; got "
+                         f"{coef8.dtype} {tuple(coef8.shape)}")
+    return coef8.numel() // 18
+
+
+def rgb8_qparams_workspace(P):
+    """Bytes of device scratch ``rgb8_qparams_into`` needs for P pixels (``rti_rgb8_qparams_workspace``)."""
+    n = int(L.lib().rti_rgb8_qparams_workspace(int(P)))
+    if n <= 0:
+        raise ValueError(f"P must be positive; got {P}")
+    return n
+
+
+def rgb8_qparams_into(coef, workspace, qparams, *, layout="pixel"):
+    """Launch ``rti_rgb8_qparams`` on preallocated tensors (no allocation, graph-capturable): the six scales and
+    six biases ``write_ptm(..., format="rgb")`` would give the maps.
+
+    coef: contiguous CUDA fp32 [3, P, 6] (layout="pixel") or [3, 6, P] ("planar"), any spatial shape in place of
+    P; workspace: a contiguous CUDA tensor of at least ``rgb8_qparams_workspace(P)`` bytes (it need not be
+    initialised); qparams: CUDA fp64 [12]."""
+    P = _rgb_maps(coef)
+    _require_cuda(workspace, "workspace")
+    need = rgb8_qparams_workspace(P)
+    if not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need \
+            or workspace.device != coef.device:
+        raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on {coef.device}; got "
+                         f"{workspace.numel() * workspace.element_size()} bytes on {workspace.device}")
+    st = L.lib().rti_rgb8_qparams(_vp(coef), _layout_id(layout), 0, P, _vp(workspace),
+                                  _rgb8_qparams_dev(qparams, coef), _stream_of(coef))
+    L.check(st, "rti_rgb8_qparams")
+    return qparams
+
+
+def rgb8_quantise_into(coef, qparams, coef8, *, layout="pixel"):
+    """Launch ``rti_rgb8_quantise`` on preallocated tensors (no allocation, graph-capturable).
+
+    coef: as ``rgb8_qparams_into``; qparams: CUDA fp64 [12] (``rgb8_qparams_into``); coef8: uint8 with 18·P
+    elements ([3, P, 6]).  Returns coef8."""
+    P = _rgb_maps(coef)
+    st = L.lib().rti_rgb8_quantise(_vp(coef), _layout_id(layout), 0, P, _rgb8_qparams_dev(qparams, coef),
+                                   _map_out(coef8, "coef8", torch.uint8, 18 * P, coef), _stream_of(coef))
+    L.check(st, "rti_rgb8_quantise")
+    return coef8
+
+
+def quantise_rgb(coef, *, layout="pixel"):
+    """Quantise three PTM-6 maps to the 18 bytes per pixel of a ``PTM_FORMAT_RGB`` file on the GPU
+    (``rti_rgb8_qparams`` then ``rti_rgb8_quantise``): the bytes, scales and biases ``write_ptm(...,
+    format="rgb")`` computes on the host, without the copy.
+
+    coef: CUDA fp32 [3, H, W, 6] / [3, P, 6] (layout="pixel") or [3, 6, H, W] / [3, 6, P] ("planar"), as ``fit``
+    returns it for a [3, N, H, W] stack.  Returns a ``QuantisedRGB`` on coef's device; ``write_ptm(path, q)``
+    writes it, ``relight_rgb8`` renders it, ``rgb8_normals`` reads its surface normals."""
+    _require_cuda(coef, "coef")
+    cl = _layout_id(layout)
+    if coef.dim() < 3 or coef.shape[0] != 3:
+        raise ValueError(f"coef must be three PTM-6 maps [3, ...]; got {tuple(coef.shape)}")
+    spatial = _coef_spatial(coef[0], 6, cl)
+    m = coef.contiguous()
+    P = _rgb_maps(m)
+    ws = torch.empty(rgb8_qparams_workspace(P), dtype=torch.uint8, device=m.device)
+    qparams = torch.empty(12, dtype=torch.float64, device=m.device)
+    coef8 = torch.empty((3,) + spatial + (6,), dtype=torch.uint8, device=m.device)
+    rgb8_qparams_into(m, ws, qparams, layout=cl)
+    rgb8_quantise_into(m, qparams, coef8, layout=cl)
+    return QuantisedRGB(coef8, qparams)
+
+
+def dequantise_rgb(q):
+    """The three fp32 PTM-6 maps [3, ..., 6] of a quantised one, with ``read_ptm``'s arithmetic: (byte − bias)·scale
+    in fp64, rounded once to fp32.  Plain torch operations on q's device, the host included (not a hot path);
+    ``relight(dequantise_rgb(q)[c], ...)`` is channel c of ``relight_rgb8(q, ...)`` bit for bit."""
+    if not isinstance(q, QuantisedRGB):
+        raise ValueError(f"q must be a QuantisedRGB; got {type(q).__name__}")
+    qp = q.qparams
+    return ((q.coef.double() - qp[6:]) * qp[:6]).float()
+
+
+def relight_rgb8_into(coef8, qparams, luv_dev, out):
+    """Launch ``rti_relight_rgb8`` on preallocated tensors (no allocation, graph-capturable).
+
+    coef8: contiguous CUDA uint8 [3, P, 6], any spatial shape in place of P; qparams: CUDA fp64 [12]; luv_dev:
+    CUDA fp64 [E, 2]; out: float32, int32 or uint8 with E·P·3 elements ([E, P, 3])."""
+    P = _rgb8_bytes(coef8)
+    _require_cuda(luv_dev, "luv")
+    if luv_dev.dtype != torch.float64 or luv_dev.dim() != 2 or luv_dev.shape[1] != 2 or luv_dev.shape[0] < 1 \
+            or not luv_dev.is_contiguous() or luv_dev.device != coef8.device:
+        raise ValueError(f"luv must be a contiguous float64 [E, 2] tensor on {coef8.device}; got {luv_dev.dtype} "
+                         f"{tuple(luv_dev.shape)} on {luv_dev.device}")
+    E = luv_dev.shape[0]
+    odt = _ENHANCED_DTYPES.get(out.dtype) if torch.is_tensor(out) else None
+    if odt is None:
+        raise ValueError("out must be a float32, int32 or uint8 tensor")
+    st = L.lib().rti_relight_rgb8(_vp(coef8), P, _rgb8_qparams_dev(qparams, coef8), _vp(luv_dev), E,
+                                  _map_out(out, "out", out.dtype, E * P * 3, coef8), odt, _stream_of(coef8))
+    L.check(st, "rti_relight_rgb8")
+    return out
+
+
+def relight_rgb8(q, lu, lv, *, out_dtype=torch.float32):
+    """Relight a quantised RGB PTM to RGB images on the GPU in one launch (``rti_relight_rgb8``), reading 18 bytes
+    per pixel once for every direction.  Channel c of the images equals ``relight(dequantise_rgb(q)[c], lu, lv)``
+    bit for bit.
+
+    q: a ``QuantisedRGB`` on the GPU.  lu, lv: scalars or E directions.  Returns [E, H, W, 3], squeezed to
+    [H, W, 3] for scalar directions, in out_dtype: float32, or int32 / uint8 converted as ``relight`` does."""
+    _quantised_rgb(q)
+    if out_dtype not in _ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    scalar = np.ndim(lu) == 0 and np.ndim(lv) == 0
+    luv = np.stack([np.asarray(lu, np.float64).ravel(), np.asarray(lv, np.float64).ravel()], -1)
+    luv_d = torch.as_tensor(np.ascontiguousarray(luv), device=q.device)
+    out = torch.empty((luv.shape[0],) + q.shape + (3,), dtype=out_dtype, device=q.device)
+    relight_rgb8_into(q.coef, q.qparams, luv_d, out)
+    return out[0] if scalar else out
+
+
+def rgb8_normals_into(coef8, qparams, normals, kind=None, peak=None, *, normal_layout="pixel", weights=None):
+    """Launch ``rti_rgb8_normals`` on preallocated tensors (no allocation, graph-capturable).
+
+    coef8 / qparams as ``relight_rgb8_into``; normals: fp32 with 3 values per pixel, [P, 3] (normal_layout="pixel")
+    or [3, P]; kind: uint8 [P] or None; peak: fp32 [P] or None; weights: None (0.299, 0.587, 0.114) or three
+    values (R, G, B)."""
+    P = _rgb8_bytes(coef8)
+    st = L.lib().rti_rgb8_normals(_vp(coef8), P, _rgb8_qparams_dev(qparams, coef8), _luma_weights(weights),
+                                  _map_out(normals, "normals", torch.float32, 3 * P, coef8),
+                                  _normal_layout_id(normal_layout),
+                                  None if kind is None else _map_out(kind, "kind", torch.uint8, P, coef8),
+                                  None if peak is None else _map_out(peak, "peak", torch.float32, P, coef8),
+                                  _stream_of(coef8))
+    L.check(st, "rti_rgb8_normals")
+    return normals
+
+
+def rgb8_normals(q, *, normal_layout="pixel", weights=None, return_kind=False, return_peak=False):
+    """Per-pixel surface normals of a quantised RGB PTM on the GPU (``rti_rgb8_normals``), from the bytes: with
+    r, g, b = ``dequantise_rgb(q)`` and l = (w0·r + w1·g) + w2·b formed in float32, ``normals(l, ...)`` bit for
+    bit, without the fp32 maps.
+
+    q: a ``QuantisedRGB`` on the GPU; weights: None (0.299, 0.587, 0.114) or three values.  Returns what
+    ``normals`` returns."""
+    _quantised_rgb(q)
+    nl = _normal_layout_id(normal_layout)
+    n, kind, peak = _normal_outputs(q.shape, nl, return_kind, return_peak, q.device)
+    rgb8_normals_into(q.coef, q.qparams, n, kind, peak, normal_layout=nl, weights=weights)
+    return _normal_results(n, kind, peak, q.shape, nl)
+
+
 # ---- light operators (RBF, fused PTM/HSH fit + evaluation) ----------------------------------
 
 def _query(qu, qv):

@@ -140,9 +140,10 @@ def _ptm_quantise(v):
     return raw, scale, bias
 
 
-def write_ptm(path, maps, format="lrgb"):
-    """Write an uncompressed PTM 1.2 file.  format="lrgb": maps [H, W, 9] (``fit_lrgb``, pixel-major);
-    format="rgb": maps [3, H, W, 6] (``fit`` of a colour stack).  Arrays or tensors on any device.
+def write_ptm(path, maps, format=None):
+    """Write an uncompressed PTM 1.2 file.  format="lrgb" (what None means for arrays): maps [H, W, 9]
+    (``fit_lrgb``, pixel-major); format="rgb": maps [3, H, W, 6] (``fit`` of a colour stack).  Arrays or tensors on
+    any device.
 
     Coefficients are quantised to bytes per coefficient plane (one scale and bias per coefficient, shared by the
     three channels of an RGB file); a plane whose values do not straddle zero loses what lies above 255·scale,
@@ -150,17 +151,29 @@ def write_ptm(path, maps, format="lrgb"):
     chroma, and the luminance is multiplied by s: the product chroma·L survives, the normalisation
     Σ w·chroma = 1 does not.  Returns path.
 
-    maps may also be a ``QuantisedLRGB`` [H, W] (``quantise_lrgb``, or ``read_ptm(path, quantised=True)``): its 9
-    bytes per pixel and 13 doubles are copied to the host and written as they are, with the same header."""
-    from .api import QuantisedLRGB
+    maps may also be a quantised object with rows, whose bytes and header doubles are copied to the host and
+    written as they are, with the same header: a ``QuantisedLRGB`` [H, W] (``quantise_lrgb``, ``read_ptm8``)
+    writes PTM_FORMAT_LRGB, a ``QuantisedRGB`` [H, W] (``quantise_rgb``, ``read_ptm8``) PTM_FORMAT_RGB.  format
+    None means the object's own; one that contradicts it raises ValueError."""
+    from .api import QuantisedLRGB, QuantisedRGB
 
     if isinstance(maps, QuantisedLRGB):
-        if format != "lrgb":
+        if format not in (None, "lrgb"):
             raise ValueError(f"a QuantisedLRGB is an LRGB payload; got format {format!r}")
         if len(maps.shape) != 2:
             raise ValueError(f"a file needs a map with rows: QuantisedLRGB [H, W]; got {maps.shape}")
         raw, rgb = maps.coef.detach().cpu().numpy(), maps.rgb.detach().cpu().numpy()
         return _ptm_write(path, b"PTM_FORMAT_LRGB", maps.shape, maps.scale, maps.bias, [raw[::-1], rgb[::-1]])
+    if isinstance(maps, QuantisedRGB):
+        if format not in (None, "rgb"):
+            raise ValueError(f"a QuantisedRGB is an RGB payload; got format {format!r}")
+        if len(maps.shape) != 2:
+            raise ValueError(f"a file needs a map with rows: QuantisedRGB [H, W]; got {maps.shape}")
+        raw = maps.coef.detach().cpu().numpy()
+        return _ptm_write(path, b"PTM_FORMAT_RGB", maps.shape, maps.scale, maps.bias,
+                          [raw[c, ::-1] for c in range(3)])
+    if format is None:
+        format = "lrgb"
     m = _host_f64(maps)
     if format == "lrgb":
         if m.ndim != 3 or m.shape[2] != 9:
@@ -217,15 +230,8 @@ def _ptm_tokens(buf, n):
     return toks, i
 
 
-def read_ptm(path, quantised=False):
-    """Read an uncompressed PTM 1.2 file -> ``(format, maps)``: ("lrgb", fp32 [H, W, 9]) or ("rgb", fp32
-    [3, H, W, 6]), rows top first as ``write_ptm`` takes them.  Any whitespace may separate the header's tokens;
-    the payload starts one byte after the last bias.  LRGB chroma is byte/255.  The LUM and JPEG formats raise
-    NotImplementedError, a bad magic or a short payload ValueError.
-
-    quantised=True keeps an LRGB file's 9 bytes per pixel: ("lrgb", ``QuantisedLRGB`` [H, W]) of host tensors,
-    rows top first, the header's scales and biases and s = 1; ``.to(device)`` moves it to the GPU for
-    ``relight_lrgb8``.  RGB files raise NotImplementedError (quantised RGB maps are not built)."""
+def _ptm_read(path):
+    """An uncompressed PTM 1.2 file -> (format, H, W, scale fp64 [6], bias fp64 [6], payload bytes), checked."""
     with open(path, "rb") as f:
         buf = f.read()
     (magic, tag), _ = _ptm_tokens(buf, 2)
@@ -245,27 +251,61 @@ def read_ptm(path, quantised=False):
     if W < 1 or H < 1:
         raise ValueError(f"PTM header: bad size {W} x {H}")
     fmt = _PTM_FORMATS[tag]
-    n = H * W
-    need = 9 * n if fmt == "lrgb" else 18 * n
+    need = (9 if fmt == "lrgb" else 18) * H * W
     data = np.frombuffer(buf, np.uint8, offset=min(end + 1, len(buf)))
     if data.size < need:
         raise ValueError(f"short PTM payload: {data.size} of {need} bytes")
-    if quantised:
-        if fmt != "lrgb":
-            raise NotImplementedError("read_ptm(quantised=True): quantised RGB (18-byte) maps are not built")
-        import torch
+    return fmt, H, W, scale, bias, data
 
-        from .api import QuantisedLRGB
 
+def _ptm_quantised(fmt, H, W, scale, bias, data):
+    """The payload as it is: a QuantisedLRGB or QuantisedRGB [H, W] of host tensors, rows top first."""
+    import torch
+
+    from .api import QuantisedLRGB, QuantisedRGB
+
+    n = H * W
+    if fmt == "lrgb":
         blocks = [data[a * n:b * n].reshape(H, W, b - a)[::-1].copy(order="C") for a, b in ((0, 6), (6, 9))]
         qparams = np.concatenate([scale, bias, [1.0]])
-        return fmt, QuantisedLRGB(*(torch.from_numpy(x) for x in blocks + [qparams]))
+        return QuantisedLRGB(*(torch.from_numpy(x) for x in blocks + [qparams]))
+    raw = data[:18 * n].reshape(3, H, W, 6)[:, ::-1].copy(order="C")
+    return QuantisedRGB(torch.from_numpy(raw), torch.from_numpy(np.concatenate([scale, bias])))
+
+
+def read_ptm(path, quantised=False):
+    """Read an uncompressed PTM 1.2 file -> ``(format, maps)``: ("lrgb", fp32 [H, W, 9]) or ("rgb", fp32
+    [3, H, W, 6]), rows top first as ``write_ptm`` takes them.  Any whitespace may separate the header's tokens;
+    the payload starts one byte after the last bias.  LRGB chroma is byte/255.  The LUM and JPEG formats raise
+    NotImplementedError, a bad magic or a short payload ValueError.
+
+    quantised=True keeps an LRGB file's 9 bytes per pixel: ("lrgb", ``QuantisedLRGB`` [H, W]) of host tensors,
+    rows top first, the header's scales and biases and s = 1; ``.to(device)`` moves it to the GPU for
+    ``relight_lrgb8``.  RGB files raise NotImplementedError here: ``read_ptm8`` keeps the bytes of either format
+    and returns a ``QuantisedRGB`` for them."""
+    fmt, H, W, scale, bias, data = _ptm_read(path)
+    n = H * W
+    if quantised:
+        if fmt != "lrgb":
+            raise NotImplementedError("read_ptm(quantised=True) keeps LRGB payloads only; read_ptm8(path) returns "
+                                      "the 18 bytes per pixel of an RGB file as a QuantisedRGB")
+        return fmt, _ptm_quantised(fmt, H, W, scale, bias, data)
     if fmt == "lrgb":
         coef = (data[:6 * n].reshape(H, W, 6)[::-1].astype(np.float64) - bias) * scale
         rgb = data[6 * n:9 * n].reshape(H, W, 3)[::-1].astype(np.float64) / 255.0
         return fmt, np.concatenate([coef, rgb], -1).astype(np.float32)
     coef = (data[:18 * n].reshape(3, H, W, 6)[:, ::-1].astype(np.float64) - bias) * scale
     return fmt, coef.astype(np.float32)
+
+
+def read_ptm8(path):
+    """Read an uncompressed PTM 1.2 file and keep its bytes -> ``(format, q)``: ("lrgb", ``QuantisedLRGB`` [H, W])
+    with s = 1, exactly what ``read_ptm(path, quantised=True)`` returns, or ("rgb", ``QuantisedRGB`` [H, W]).  Host
+    tensors, rows top first, the header's scales and biases; ``.to(device)`` moves the object to the GPU for
+    ``relight_lrgb8`` or ``relight_rgb8`` / ``rgb8_normals``.  ``dequantise_lrgb`` / ``dequantise_rgb`` of it equal
+    ``read_ptm(path)[1]`` to the bit.  Errors as ``read_ptm``."""
+    fmt, H, W, scale, bias, data = _ptm_read(path)
+    return fmt, _ptm_quantised(fmt, H, W, scale, bias, data)
 
 
 # ---- .rti files (HSH 1.2, uncompressed RGB hemispherical harmonics; layout restated in DESIGN.md §4.9) --------

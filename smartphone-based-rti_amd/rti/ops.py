@@ -1,7 +1,8 @@
 """PyTorch custom ops over the C ABI: ``torch.ops.rti.fit_shared`` / ``fit_shared_residual`` /
 ``fit_robust`` / ``fit_accumulate`` / ``fit_accum_solve`` / ``fit_residual`` / ``relight`` / ``ptm_normals`` /
 ``relight_enhanced`` / ``map_unsharp`` / ``shade_normals`` / ``lrgb_from_rgb`` / ``relight_lrgb`` /
-``lrgb_quantise`` / ``relight_lrgb8`` / ``hsh_quantise`` / ``relight_hsh8`` / ``hsh_normals`` / ``hsh8_normals``.
+``lrgb_quantise`` / ``relight_lrgb8`` / ``hsh_quantise`` / ``relight_hsh8`` / ``hsh_normals`` / ``hsh8_normals`` /
+``rgb8_quantise`` / ``relight_rgb8`` / ``rgb8_normals``.
 
 They let the fit and relight kernels sit inside torch programs (and
 ``torch.library`` fake-tensor tracing) while the compute stays in librti's
@@ -523,3 +524,72 @@ def hsh8_normals(coef8: torch.Tensor, qparams: torch.Tensor, normals_planar: boo
 @hsh8_normals.register_fake
 def _(coef8, qparams, normals_planar=False, grid=10, weights=None):
     return _normal_triple(coef8, coef8.shape[0], normals_planar)
+
+
+@torch.library.custom_op("rti::rgb8_quantise", mutates_args=())
+def rgb8_quantise(coef: torch.Tensor, planar: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+    """Three PTM-6 maps -> their PTM_FORMAT_RGB bytes and header values (``rti_rgb8_qparams`` then
+    ``rti_rgb8_quantise``).  coef CUDA fp32 [3, P, 6] (or [3, 6, P] if planar) -> (coef8 uint8 [3, P, 6], qparams
+    fp64 [12])."""
+    api._require_cuda(coef, "coef")
+    if coef.dim() != 3 or coef.shape[0] != 3 or coef.shape[1 if planar else 2] != 6:
+        raise ValueError(f"coef must be {'[3, 6, P]' if planar else '[3, P, 6]'}; got {tuple(coef.shape)}")
+    P = coef.shape[2 if planar else 1]
+    layout = "planar" if planar else "pixel"
+    m = coef.contiguous()
+    ws = coef.new_empty((api.rgb8_qparams_workspace(P),), dtype=torch.uint8)
+    qparams = coef.new_empty((12,), dtype=torch.float64)
+    coef8 = coef.new_empty((3, P, 6), dtype=torch.uint8)
+    api.rgb8_qparams_into(m, ws, qparams, layout=layout)
+    api.rgb8_quantise_into(m, qparams, coef8, layout=layout)
+    return coef8, qparams
+
+
+@rgb8_quantise.register_fake
+def _(coef, planar=False):
+    P = coef.shape[2 if planar else 1]
+    return coef.new_empty((3, P, 6), dtype=torch.uint8), coef.new_empty((12,), dtype=torch.float64)
+
+
+def _rgb8_pixels(coef8):
+    if coef8.dim() != 3 or coef8.shape[0] != 3 or coef8.shape[2] != 6:
+        raise ValueError(f"coef8 must be [3, P, 6]; got {tuple(coef8.shape)}")
+    return coef8.shape[1]
+
+
+@torch.library.custom_op("rti::relight_rgb8", mutates_args=())
+def relight_rgb8(coef8: torch.Tensor, qparams: torch.Tensor, luv: torch.Tensor,
+                 out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """RGB images of a quantised RGB PTM (``rti_relight_rgb8``).  coef8 CUDA uint8 [3, P, 6], qparams fp64 [12],
+    luv [E, 2] -> [E, P, 3] in out_dtype (float32, int32 or uint8)."""
+    api._require_cuda(coef8, "coef8")
+    P = _rgb8_pixels(coef8)
+    if out_dtype not in api._ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    luv_d = luv.detach().to(device=coef8.device, dtype=torch.float64).contiguous()
+    out = coef8.new_empty((luv.shape[0], P, 3), dtype=out_dtype)
+    return api.relight_rgb8_into(coef8.contiguous(), qparams.contiguous(), luv_d, out)
+
+
+@relight_rgb8.register_fake
+def _(coef8, qparams, luv, out_dtype=torch.float32):
+    return coef8.new_empty((luv.shape[0], coef8.shape[1], 3), dtype=out_dtype)
+
+
+@torch.library.custom_op("rti::rgb8_normals", mutates_args=())
+def rgb8_normals(coef8: torch.Tensor, qparams: torch.Tensor, normals_planar: bool = False,
+                 weights: Optional[Sequence[float]] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Surface normals of a quantised RGB PTM (``rti_rgb8_normals``).  coef8 CUDA uint8 [3, P, 6], qparams fp64
+    [12], weights None (0.299, 0.587, 0.114) or 3 values -> ``(normals, kind, peak)``: normals fp32 [P, 3] (or
+    [3, P] if normals_planar), kind uint8 [P], peak fp32 [P]."""
+    api._require_cuda(coef8, "coef8")
+    P = _rgb8_pixels(coef8)
+    normals, kind, peak = _normal_triple(coef8, P, normals_planar)
+    api.rgb8_normals_into(coef8.contiguous(), qparams.contiguous(), normals, kind, peak,
+                          normal_layout="planar" if normals_planar else "pixel", weights=weights)
+    return normals, kind, peak
+
+
+@rgb8_normals.register_fake
+def _(coef8, qparams, normals_planar=False, weights=None):
+    return _normal_triple(coef8, coef8.shape[1], normals_planar)
