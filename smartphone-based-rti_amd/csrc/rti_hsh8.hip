@@ -17,10 +17,8 @@
 // Anything the pieces cannot serve (a pointer off its alignment, the last partial wave) loads and stores per
 // lane, through the same per-pixel functions.
 //
-// The extremes are order-independent (min and max of finite values; a zero minimum is stored as +0), so the
-// reduction tree does not show in the result: a lane folds its pixels into 2k floats, a wave folds its lanes with
-// shuffles, a workgroup its waves through LDS, and every workgroup writes its 2k partials to the workspace; a
-// one-workgroup tail folds those.  No atomics, and no workspace word is read that this call did not write.
+// The extremes pass is rti_quant8.h's, with a partial of 2k floats: the k minima and the k maxima over the three
+// channels.  A zero minimum is stored as +0, so the bias does not depend on the order of the reduction either.
 #include <hip/hip_runtime.h>
 
 #include <cfloat>
@@ -30,21 +28,17 @@
 #include "rti_basis.h"
 #include "rti_convert.h"
 #include "rti_hsh_px.h"
+#include "rti_quant8.h"
 #include "rti_stack.h"
 
 namespace rti {
 namespace {
 
 using namespace hsh_px;  // the chain, the slab runs and the dequantisation, shared with rti_hsh_normals.hip
+using namespace quant8;
 
-constexpr int ECH = 64;             // directions per basis table in LDS (rti_relight's)
-constexpr int QP_MAX_BLOCKS = 768;  // the extremes' grid: 3 workgroups per CU of 256, each striding over chunks
-constexpr int CHUNK = 256;          // pixels of a workgroup
-
-inline int64_t qparams_blocks(int64_t P) {
-  const int64_t chunks = (P + CHUNK - 1) / CHUNK;
-  return chunks < QP_MAX_BLOCKS ? chunks : QP_MAX_BLOCKS;
-}
+constexpr int ECH = 64;     // directions per basis table in LDS (rti_relight's)
+constexpr int CHUNK = 256;  // pixels of a workgroup
 
 // ---- the three fp32 maps of a pixel -----------------------------------------------------------------------------
 // x[c][j] of pixel wave_px + lane.  staged (wave-uniform; pixel-major, a full wave, 16-byte aligned rows): the
@@ -75,35 +69,7 @@ __device__ __forceinline__ void load_px(const float* __restrict__ coef, int64_t 
 }
 
 // ---- extremes ----------------------------------------------------------------------------------------------------
-// q[j], q[K + j]: min and max of the finite values of term j in the three channels.  A term without a finite
-// value keeps lo = +inf > hi = -inf.
-
-template <int K>
-__device__ __forceinline__ float ext_fold(int i, float a, float b) { return i < K ? fminf(a, b) : fmaxf(a, b); }
-
-template <int K>
-__device__ __forceinline__ void ext_init(float (&q)[2 * K]) {
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    q[j] = INFINITY;
-    q[K + j] = -INFINITY;
-  }
-}
-
-// the workgroup's 256 lanes -> thread i < 2K returns value i
-template <int K>
-__device__ __forceinline__ float ext_block_fold(float (&q)[2 * K], float (*part)[2 * K]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < 2 * K; ++i) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) q[i] = ext_fold<K>(i, q[i], __shfl_xor(q[i], m, 64));
-    if (lane == 0) part[wave][i] = q[i];
-  }
-  __syncthreads();
-  const int i = threadIdx.x < 2 * K ? threadIdx.x : 0;
-  return ext_fold<K>(i, ext_fold<K>(i, part[0][i], part[1][i]), ext_fold<K>(i, part[2][i], part[3][i]));
-}
+// q[j], q[K + j]: min and max of the finite values of term j in the three channels.
 
 template <int K, int CL>
 __global__ void __launch_bounds__(256)
@@ -123,11 +89,7 @@ hsh_extremes_k(const float* __restrict__ coef, int64_t cs, int64_t P, int vin, f
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch)
 #pragma unroll
-      for (int j = 0; j < K; ++j)
-        if (fabsf(x[ch][j]) <= FLT_MAX) {  // false for NaN
-          q[j] = fminf(q[j], x[ch][j]);
-          q[K + j] = fmaxf(q[K + j], x[ch][j]);
-        }
+      for (int j = 0; j < K; ++j) ext_update(q[j], q[K + j], x[ch][j]);
   }
   const float r = ext_block_fold<K>(q, part);
   if (threadIdx.x < 2 * K) partial[(int64_t)blockIdx.x * (2 * K) + threadIdx.x] = r;
@@ -140,14 +102,7 @@ hsh_qparams_k(const float* __restrict__ partial, int n, float* __restrict__ qpar
 #pragma clang fp contract(off)
   __shared__ float part[4][2 * K];
   __shared__ float fin[2 * K];
-  float q[2 * K];
-  ext_init<K>(q);
-  for (int b = threadIdx.x; b < n; b += 256)
-#pragma unroll
-    for (int i = 0; i < 2 * K; ++i) q[i] = ext_fold<K>(i, q[i], partial[(int64_t)b * (2 * K) + i]);
-  const float r = ext_block_fold<K>(q, part);
-  if (threadIdx.x < 2 * K) fin[threadIdx.x] = r;
-  __syncthreads();
+  fold_partials<K>(partial, n, part, fin);
   if (threadIdx.x < K) {
     const int j = threadIdx.x;
     const float lo = fin[j], hi = fin[K + j];
@@ -159,12 +114,6 @@ hsh_qparams_k(const float* __restrict__ partial, int n, float* __restrict__ qpar
 }
 
 // ---- per-pixel quantisation (load_steps and dequantise_px: rti_hsh_px.h) ----------------------------------------
-
-// rint(t) clipped to a byte; NaN -> 0
-__device__ __forceinline__ uint32_t byte_of(double t) {
-  const double r = rint(t);
-  return (uint32_t)(int)(r > 0.0 ? (r < 255.0 ? r : 255.0) : 0.0);
-}
 
 // three fp32 maps of a pixel -> its 3K bytes, [c][j], packed as lane_words packs them
 template <int K>
@@ -373,7 +322,7 @@ inline int maps_vec(const float* coef, int layout, int64_t cs) {
 using namespace rti;
 
 extern "C" int64_t rti_hsh_qparams_workspace(int k, int64_t P) {
-  return P < 1 || (k != 9 && k != 16) ? 0 : qparams_blocks(P) * 2 * k * (int64_t)sizeof(float);
+  return P < 1 || (k != 9 && k != 16) ? 0 : qparams_blocks(P, CHUNK) * 2 * k * (int64_t)sizeof(float);
 }
 
 extern "C" int rti_hsh_qparams(const float* coef, int basis, int coef_layout, int64_t coef_channel_stride, int64_t P,
@@ -385,7 +334,7 @@ extern "C" int rti_hsh_qparams(const float* coef, int basis, int coef_layout, in
     return fail(RTI_ERR_BAD_ARG, "%s: workspace and qparams must be 4-byte aligned", E);
   const int k = basis_terms(basis);
   const int64_t cs = coef_channel_stride ? coef_channel_stride : P * k;
-  const int blocks = (int)qparams_blocks(P);
+  const int blocks = (int)qparams_blocks(P, CHUNK);
   float* partial = static_cast<float*>(workspace);
   const HshArgs a{coef, coef_layout, cs, P, maps_vec(coef, coef_layout, cs), (hipStream_t)stream};
   note_launches(2);

@@ -10,11 +10,9 @@
 // dot6 / rgb_of (rti_lrgb_px.h).
 //
 // All kernels keep rti_relight's lane map (a lane owns 4 consecutive pixels, a wave 256, a block 1024) and
-// rti_lrgb.hip's loads of the fp32 map.  The extremes are order-independent (min and max of finite values), so
-// the reduction tree does not show in the result: a lane folds its pixels into 13 floats, a wave folds its lanes
-// with shuffles, a workgroup its waves through LDS, and every workgroup of the grid writes its 13 partials to the
-// workspace; a one-workgroup tail folds those and forms the 13 doubles.  No atomics, and no workspace word is read
-// that this call did not write.  The byte blocks are read and written as whole dwords per lane (24 B + 12 B).
+// rti_lrgb.hip's loads of the fp32 map.  The extremes pass is rti_quant8.h's, with a partial of 13 floats: the six
+// minima, the six maxima and the chroma max.  The byte blocks are read and written as whole dwords per lane
+// (24 B + 12 B).
 //
 // A launch whose P is no multiple of 4 or whose pointers are not aligned for the vector accesses, and the last
 // partial wave of any launch, take one pixel per lane through the same per-pixel functions.
@@ -27,62 +25,26 @@
 #include "rti_basis.h"
 #include "rti_convert.h"
 #include "rti_lrgb_px.h"
+#include "rti_quant8.h"
 #include "rti_stack.h"
 
 namespace rti {
 namespace {
 
 using namespace lrgb_px;
+using namespace quant8;
 
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int NQ = 13;               // a partial: the chroma max, lo[6], hi[6]; qparams: scale[6], bias[6], s
-constexpr int QP_MAX_BLOCKS = 768;   // the extremes' grid: 3 workgroups per CU of 256, each striding over chunks
-
-inline int64_t qparams_blocks(int64_t P) {
-  const int64_t chunks = (P + 1023) / 1024;
-  return chunks < QP_MAX_BLOCKS ? chunks : QP_MAX_BLOCKS;
-}
+constexpr int NQ = 2 * K + 1;  // a partial: lo[6], hi[6], the chroma max; qparams: scale[6], bias[6], s
 
 // ---- extremes ----------------------------------------------------------------------------------------------------
-// q[0]: max of the finite chroma values; q[1 + j], q[7 + j]: min and max of the finite values of plane j.
-// A plane without a finite value keeps lo = +inf > hi = -inf.
-
-__device__ __forceinline__ void ext_init(float (&q)[NQ]) {
-  q[0] = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    q[1 + j] = INFINITY;
-    q[7 + j] = -INFINITY;
-  }
-}
-
-__device__ __forceinline__ float ext_fold(int i, float a, float b) { return i >= 1 && i <= K ? fminf(a, b) : fmaxf(a, b); }
+// q[j], q[6 + j]: min and max of the finite values of plane j; q[12]: max of the finite chroma values.
 
 __device__ __forceinline__ void ext_pixel(float (&q)[NQ], const float (&m)[NL]) {
 #pragma unroll
-  for (int j = 0; j < K; ++j)
-    if (fabsf(m[j]) <= FLT_MAX) {  // false for NaN
-      q[1 + j] = fminf(q[1 + j], m[j]);
-      q[7 + j] = fmaxf(q[7 + j], m[j]);
-    }
+  for (int j = 0; j < K; ++j) ext_update(q[j], q[K + j], m[j]);
 #pragma unroll
   for (int c = 0; c < 3; ++c)
-    if (fabsf(m[K + c]) <= FLT_MAX) q[0] = fmaxf(q[0], m[K + c]);
-}
-
-// the workgroup's 256 lanes -> part[0] (valid in thread 0 .. NQ-1 after the call: thread i returns value i)
-__device__ __forceinline__ float ext_block_fold(float (&q)[NQ], float (*part)[NQ]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < NQ; ++i) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) q[i] = ext_fold(i, q[i], __shfl_xor(q[i], m, 64));
-    if (lane == 0) part[wave][i] = q[i];
-  }
-  __syncthreads();
-  const int i = threadIdx.x < NQ ? threadIdx.x : 0;
-  return ext_fold(i, ext_fold(i, part[0][i], part[1][i]), ext_fold(i, part[2][i], part[3][i]));
+    if (is_finite(m[K + c])) q[2 * K] = fmaxf(q[2 * K], m[K + c]);
 }
 
 template <int CL>
@@ -94,7 +56,7 @@ lrgb_extremes_k(const float* __restrict__ lrgb, int64_t P, int vec, float* __res
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   floatx4* slab = slabs + wave * SLAB;
   float q[NQ];
-  ext_init(q);
+  ext_init<K>(q);
   const int64_t chunks = (P + 1023) / 1024;
   for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
     const int64_t wave_px = (c * 4 + wave) * 256;
@@ -114,96 +76,47 @@ lrgb_extremes_k(const float* __restrict__ lrgb, int64_t P, int vec, float* __res
       }
     }
   }
-  const float r = ext_block_fold(q, part);
+  const float r = ext_block_fold<K>(q, part);
   if (threadIdx.x < NQ) partial[(int64_t)blockIdx.x * NQ + threadIdx.x] = r;
 }
 
 // n partials -> qparams; one workgroup
 __global__ void __launch_bounds__(256)
 lrgb_qparams_k(const float* __restrict__ partial, int n, double* __restrict__ qparams) {
-#pragma clang fp contract(off)
   __shared__ float part[4][NQ];
   __shared__ float fin[NQ];
-  float q[NQ];
-  ext_init(q);
-  for (int b = threadIdx.x; b < n; b += 256)
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) q[i] = ext_fold(i, q[i], partial[(int64_t)b * NQ + i]);
-  const float r = ext_block_fold(q, part);
-  if (threadIdx.x < NQ) fin[threadIdx.x] = r;
-  __syncthreads();
-  if (threadIdx.x == 0) qparams[2 * K] = fin[0] > 0.0f ? (double)fin[0] : 1.0;
+  fold_partials<K>(partial, n, part, fin);
+  const double s = fin[2 * K] > 0.0f ? (double)fin[2 * K] : 1.0;
+  if (threadIdx.x == 0) qparams[2 * K] = s;
   if (threadIdx.x < K) {
     const int j = threadIdx.x;
-    const double s = fin[0] > 0.0f ? (double)fin[0] : 1.0;
-    const bool has = fin[1 + j] <= fin[7 + j];  // the plane has a finite value
-    const double LO = (double)fin[1 + j] * s, HI = (double)fin[7 + j] * s;
-    const double scale = has && HI > LO ? (HI - LO) / 255.0 : 1.0;
-    double bias = 0.0;
-    if (has) {
-      const double b = rint(-LO / scale);
-      bias = b > 0.0 ? (b < 255.0 ? b : 255.0) : 0.0;  // -0.0 -> 0.0
-    }
-    qparams[j] = scale;
-    qparams[K + j] = bias;
+    ptm_scale_bias(fin[j], fin[K + j], s, qparams[j], qparams[K + j]);
   }
 }
 
 // ---- per-pixel quantisation and dequantisation (fp64, no contraction) -------------------------------------------
 
-struct QParams {
-  double scale[K], bias[K], s;
-};
-
-__device__ __forceinline__ QParams load_qparams(const double* __restrict__ qparams) {
-  QParams q;
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    q.scale[j] = qparams[j];
-    q.bias[j] = qparams[K + j];
-  }
-  q.s = qparams[2 * K];
-  return q;
-}
-
-// rint(t) clipped to a byte; NaN -> 0
-__device__ __forceinline__ uint8_t byte_of(double t) {
-  const double r = rint(t);
-  return (uint8_t)(int)(r > 0.0 ? (r < 255.0 ? r : 255.0) : 0.0);
-}
-
 // one fp32 LRGB pixel -> its 6 coefficient bytes and 3 colour bytes (rti/io.py: _ptm_quantise, write_ptm)
-__device__ __forceinline__ void quantise_px(const float (&m)[NL], const QParams& q, uint8_t (&cb)[K],
+__device__ __forceinline__ void quantise_px(const float (&m)[NL], const QParams<K>& q, double s, uint8_t (&cb)[K],
                                             uint8_t (&rb)[3]) {
 #pragma clang fp contract(off)
 #pragma unroll
   for (int j = 0; j < K; ++j) {
     const double a = (double)m[j];
-    const double x = a * q.s;
-    cb[j] = a != a ? (uint8_t)(int)q.bias[j] : byte_of(x / q.scale[j] + q.bias[j]);
+    cb[j] = coef_byte(a, a * s, q.scale[j], q.bias[j]);
   }
 #pragma unroll
-  for (int c = 0; c < 3; ++c) rb[c] = byte_of(255.0 * (double)m[K + c] / q.s);
+  for (int c = 0; c < 3; ++c) rb[c] = (uint8_t)byte_of(255.0 * (double)m[K + c] / s);
 }
 
 // 9 bytes -> the fp32 LRGB pixel read_ptm builds from them
-__device__ __forceinline__ void dequantise_px(const uint8_t (&cb)[K], const uint8_t (&rb)[3], const QParams& q,
+__device__ __forceinline__ void dequantise_px(const uint8_t (&cb)[K], const uint8_t (&rb)[3], const QParams<K>& q,
                                               float (&m)[NL]) {
 #pragma clang fp contract(off)
 #pragma unroll
   for (int j = 0; j < K; ++j) m[j] = (float)(((double)cb[j] - q.bias[j]) * q.scale[j]);
 #pragma unroll
   for (int c = 0; c < 3; ++c) m[K + c] = (float)((double)rb[c] / 255.0);
-}
-
-// NB bytes (a multiple of 4) of a lane as dwords
-template <int NB>
-__device__ __forceinline__ void store_dwords(uint8_t* __restrict__ dst, const uint8_t* f) {
-  uint32_t* o4 = reinterpret_cast<uint32_t*>(dst);
-#pragma unroll
-  for (int w = 0; w < NB / 4; ++w)
-    o4[w] = (uint32_t)f[4 * w] | ((uint32_t)f[4 * w + 1] << 8) | ((uint32_t)f[4 * w + 2] << 16) |
-            ((uint32_t)f[4 * w + 3] << 24);
 }
 
 // ---- kernels ------------------------------------------------------------------------------------------------------
@@ -218,13 +131,14 @@ lrgb_quantise_k(const float* __restrict__ lrgb, int64_t P, int vec, const double
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
   if (wave_px >= P) return;
-  const QParams q = load_qparams(qparams);
+  const QParams<K> q = load_qparams<K>(qparams);
+  const double s = qparams[2 * K];
   if (vec && wave_px + 256 <= P) {  // wave-uniform
     float m[4][NL];
     load_wave<NL, CL>(lrgb, P, wave_px, lane, slabs + wave * SLAB, m);
     uint8_t cb[4][K], rb[4][3];
 #pragma unroll
-    for (int v = 0; v < 4; ++v) quantise_px(m[v], q, cb[v], rb[v]);
+    for (int v = 0; v < 4; ++v) quantise_px(m[v], q, s, cb[v], rb[v]);
     const int64_t p0 = wave_px + 4 * lane;
     store_dwords<4 * K>(coef8 + p0 * K, &cb[0][0]);
     store_dwords<12>(rgb8 + p0 * 3, &rb[0][0]);
@@ -236,7 +150,7 @@ lrgb_quantise_k(const float* __restrict__ lrgb, int64_t P, int vec, const double
     float m[NL];
     load_pixel<NL, CL>(lrgb, P, p, m);
     uint8_t cb[K], rb[3];
-    quantise_px(m, q, cb, rb);
+    quantise_px(m, q, s, cb, rb);
 #pragma unroll
     for (int i = 0; i < K; ++i) coef8[p * K + i] = cb[i];
 #pragma unroll
@@ -255,8 +169,8 @@ relight_lrgb8_k(const uint8_t* __restrict__ coef8, const uint8_t* __restrict__ r
   const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
   if (wave_px >= P) return;
   floatx4* slab = slabs + wave * SLAB;
-  const QParams q = load_qparams(qparams);  // s is not used: the colour bytes are chroma·255
-  if (vec && wave_px + 256 <= P) {          // wave-uniform
+  const QParams<K> q = load_qparams<K>(qparams);  // s is not used: the colour bytes are chroma·255
+  if (vec && wave_px + 256 <= P) {                // wave-uniform
     const int64_t p0 = wave_px + 4 * lane;
     union {
       u32x2 v[3];
@@ -331,7 +245,7 @@ int check_lrgb_layout(const char* entry, int layout) {
 using namespace rti;
 
 extern "C" int64_t rti_lrgb_qparams_workspace(int64_t P) {
-  return P < 1 ? 0 : qparams_blocks(P) * NQ * (int64_t)sizeof(float);
+  return P < 1 ? 0 : qparams_blocks(P, 1024) * NQ * (int64_t)sizeof(float);
 }
 
 extern "C" int rti_lrgb_qparams(const float* lrgb, int lrgb_layout, int64_t P, void* workspace, double* qparams,
@@ -342,7 +256,7 @@ extern "C" int rti_lrgb_qparams(const float* lrgb, int lrgb_layout, int64_t P, v
   if (int st = check_lrgb_layout(E, lrgb_layout)) return st;
   if (!aligned_to(workspace, 4) || !aligned_to(qparams, 8))
     return fail(RTI_ERR_BAD_ARG, "%s: workspace must be 4-byte and qparams 8-byte aligned", E);
-  const int blocks = (int)qparams_blocks(P);
+  const int blocks = (int)qparams_blocks(P, 1024);
   const int vec = P % 4 == 0 && aligned_to(lrgb, 16) ? 1 : 0;
   float* partial = static_cast<float*>(workspace);
   note_launches(2);

@@ -19,11 +19,8 @@
 //
 // All kernels keep rti_relight's lane map (a lane owns 4 consecutive pixels, a wave 256, a block 1024) and
 // rti_lrgb_px.h's loads of the fp32 maps.  A lane's 24 bytes of a channel block are contiguous: they are read as
-// three 8-byte loads per block and written as six dwords.  The extremes are order-independent (min and max of finite
-// values), so the reduction tree does not show in the result: a lane folds its pixels into 12 floats, a wave folds
-// its lanes with shuffles, a workgroup its waves through LDS, and every workgroup of the grid writes its 12 partials
-// to the workspace; a one-workgroup tail folds those and forms the 12 doubles.  No atomics, and no workspace word is
-// read that this call did not write.
+// three 8-byte loads per block and written as six dwords.  The extremes pass is rti_quant8.h's, with a partial of 12
+// floats: the six minima and the six maxima over the three channels.
 //
 // A launch whose P is no multiple of 4 or whose pointers are not aligned for the vector accesses, and the last
 // partial wave of any launch, take one pixel per lane through the same per-pixel functions.
@@ -38,6 +35,7 @@
 #include "rti_hsh_px.h"
 #include "rti_lrgb_px.h"
 #include "rti_ptm_px.h"
+#include "rti_quant8.h"
 #include "rti_stack.h"
 
 namespace rti {
@@ -45,52 +43,16 @@ namespace {
 
 using namespace lrgb_px;  // K = 6, the wave loads of fp32 maps, the staged row stores
 using hsh_px::dot_k;      // rti_relight's fp32 chain
+using namespace quant8;
 
-typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int NQ = 2 * K;            // a partial: lo[6], hi[6]; qparams: scale[6], bias[6]
-constexpr int QP_MAX_BLOCKS = 768;   // the extremes' grid: 3 workgroups per CU of 256, each striding over chunks
-
-inline int64_t qparams_blocks(int64_t P) {
-  const int64_t chunks = (P + 1023) / 1024;
-  return chunks < QP_MAX_BLOCKS ? chunks : QP_MAX_BLOCKS;
-}
+constexpr int NQ = 2 * K;  // a partial: lo[6], hi[6]; qparams: scale[6], bias[6]
 
 // ---- extremes ----------------------------------------------------------------------------------------------------
-// q[j], q[6 + j]: min and max of the finite values of plane j in the three channels.  A plane without a finite
-// value keeps lo = +inf > hi = -inf.
-
-__device__ __forceinline__ void ext_init(float (&q)[NQ]) {
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    q[j] = INFINITY;
-    q[K + j] = -INFINITY;
-  }
-}
-
-__device__ __forceinline__ float ext_fold(int i, float a, float b) { return i < K ? fminf(a, b) : fmaxf(a, b); }
+// q[j], q[6 + j]: min and max of the finite values of plane j in the three channels.
 
 __device__ __forceinline__ void ext_pixel(float (&q)[NQ], const float (&m)[K]) {
 #pragma unroll
-  for (int j = 0; j < K; ++j)
-    if (fabsf(m[j]) <= FLT_MAX) {  // false for NaN
-      q[j] = fminf(q[j], m[j]);
-      q[K + j] = fmaxf(q[K + j], m[j]);
-    }
-}
-
-// the workgroup's 256 lanes -> thread i < NQ returns value i
-__device__ __forceinline__ float ext_block_fold(float (&q)[NQ], float (*part)[NQ]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < NQ; ++i) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) q[i] = ext_fold(i, q[i], __shfl_xor(q[i], m, 64));
-    if (lane == 0) part[wave][i] = q[i];
-  }
-  __syncthreads();
-  const int i = threadIdx.x < NQ ? threadIdx.x : 0;
-  return ext_fold(i, ext_fold(i, part[0][i], part[1][i]), ext_fold(i, part[2][i], part[3][i]));
+  for (int j = 0; j < K; ++j) ext_update(q[j], q[K + j], m[j]);
 }
 
 template <int CL>
@@ -102,7 +64,7 @@ rgb_extremes_k(const float* __restrict__ coef, int64_t cs, int64_t P, int vec, f
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   floatx4* slab = slabs + wave * SLAB;
   float q[NQ];
-  ext_init(q);
+  ext_init<K>(q);
   const int64_t chunks = (P + 1023) / 1024;
   for (int64_t c = blockIdx.x; c < chunks; c += gridDim.x) {
     const int64_t wave_px = (c * 4 + wave) * 256;
@@ -128,79 +90,31 @@ rgb_extremes_k(const float* __restrict__ coef, int64_t cs, int64_t P, int vec, f
       }
     }
   }
-  const float r = ext_block_fold(q, part);
+  const float r = ext_block_fold<K>(q, part);
   if (threadIdx.x < NQ) partial[(int64_t)blockIdx.x * NQ + threadIdx.x] = r;
 }
 
 // n partials -> qparams; one workgroup
 __global__ void __launch_bounds__(256)
 rgb_qparams_k(const float* __restrict__ partial, int n, double* __restrict__ qparams) {
-#pragma clang fp contract(off)
   __shared__ float part[4][NQ];
   __shared__ float fin[NQ];
-  float q[NQ];
-  ext_init(q);
-  for (int b = threadIdx.x; b < n; b += 256)
-#pragma unroll
-    for (int i = 0; i < NQ; ++i) q[i] = ext_fold(i, q[i], partial[(int64_t)b * NQ + i]);
-  const float r = ext_block_fold(q, part);
-  if (threadIdx.x < NQ) fin[threadIdx.x] = r;
-  __syncthreads();
+  fold_partials<K>(partial, n, part, fin);
   if (threadIdx.x < K) {
     const int j = threadIdx.x;
-    const bool has = fin[j] <= fin[K + j];  // the plane has a finite value
-    const double LO = (double)fin[j], HI = (double)fin[K + j];
-    const double scale = has && HI > LO ? (HI - LO) / 255.0 : 1.0;
-    double bias = 0.0;
-    if (has) {
-      const double b = rint(-LO / scale);
-      bias = b > 0.0 ? (b < 255.0 ? b : 255.0) : 0.0;  // -0.0 -> 0.0
-    }
-    qparams[j] = scale;
-    qparams[K + j] = bias;
+    ptm_scale_bias(fin[j], fin[K + j], 1.0, qparams[j], qparams[K + j]);
   }
 }
 
 // ---- per-pixel quantisation (fp64, no contraction) ---------------------------------------------------------------
 
-struct QParams {
-  double scale[K], bias[K];
-};
-
-__device__ __forceinline__ QParams load_qparams(const double* __restrict__ qparams) {
-  QParams q;
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    q.scale[j] = qparams[j];
-    q.bias[j] = qparams[K + j];
-  }
-  return q;
-}
-
-// rint(t) clipped to a byte; NaN -> 0
-__device__ __forceinline__ uint8_t byte_of(double t) {
-  const double r = rint(t);
-  return (uint8_t)(int)(r > 0.0 ? (r < 255.0 ? r : 255.0) : 0.0);
-}
-
 // six fp32 coefficients of one channel of a pixel -> their bytes (rti/io.py: _ptm_quantise)
-__device__ __forceinline__ void quantise_px(const float (&m)[K], const QParams& q, uint8_t (&cb)[K]) {
-#pragma clang fp contract(off)
+__device__ __forceinline__ void quantise_px(const float (&m)[K], const QParams<K>& q, uint8_t (&cb)[K]) {
 #pragma unroll
   for (int j = 0; j < K; ++j) {
     const double x = (double)m[j];
-    cb[j] = x != x ? (uint8_t)(int)q.bias[j] : byte_of(x / q.scale[j] + q.bias[j]);
+    cb[j] = coef_byte(x, x, q.scale[j], q.bias[j]);
   }
-}
-
-// NB bytes (a multiple of 4) of a lane as dwords
-template <int NB>
-__device__ __forceinline__ void store_dwords(uint8_t* __restrict__ dst, const uint8_t* f) {
-  uint32_t* o4 = reinterpret_cast<uint32_t*>(dst);
-#pragma unroll
-  for (int w = 0; w < NB / 4; ++w)
-    o4[w] = (uint32_t)f[4 * w] | ((uint32_t)f[4 * w + 1] << 8) | ((uint32_t)f[4 * w + 2] << 16) |
-            ((uint32_t)f[4 * w + 3] << 24);
 }
 
 // ---- dequantisation: six 256-entry tables per workgroup ---------------------------------------------------------
@@ -267,7 +181,7 @@ rgb_quantise_k(const float* __restrict__ coef, int64_t cs, int64_t P, int vec, c
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
   if (wave_px >= P) return;
-  const QParams q = load_qparams(qparams);
+  const QParams<K> q = load_qparams<K>(qparams);
   if (vec && wave_px + 256 <= P) {  // wave-uniform
     const int64_t p0 = wave_px + 4 * lane;
 #pragma unroll 1
@@ -460,7 +374,7 @@ inline int maps_vec(const float* coef, int64_t cs, int64_t P) {
 using namespace rti;
 
 extern "C" int64_t rti_rgb8_qparams_workspace(int64_t P) {
-  return P < 1 ? 0 : qparams_blocks(P) * NQ * (int64_t)sizeof(float);
+  return P < 1 ? 0 : qparams_blocks(P, 1024) * NQ * (int64_t)sizeof(float);
 }
 
 extern "C" int rti_rgb8_qparams(const float* coef, int coef_layout, int64_t coef_channel_stride, int64_t P,
@@ -471,7 +385,7 @@ extern "C" int rti_rgb8_qparams(const float* coef, int coef_layout, int64_t coef
   if (!aligned_to(workspace, 4) || !aligned_to(qparams, 8))
     return fail(RTI_ERR_BAD_ARG, "%s: workspace must be 4-byte and qparams 8-byte aligned", E);
   const int64_t cs = coef_channel_stride ? coef_channel_stride : P * K;
-  const int blocks = (int)qparams_blocks(P);
+  const int blocks = (int)qparams_blocks(P, 1024);
   const int vec = maps_vec(coef, cs, P);
   float* partial = static_cast<float*>(workspace);
   note_launches(2);

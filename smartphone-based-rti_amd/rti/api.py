@@ -1323,9 +1323,140 @@ def lrgb_luminance(lrgb, layout="planar"):
     return lrgb[:6]
 
 
+# ---- 8-bit maps: what the three quantised objects and their entry points share ----------------
+
+class _Quantised:
+    """The base of ``QuantisedLRGB``, ``QuantisedHSH`` and ``QuantisedRGB``: a contiguous uint8 ``coef`` and a
+    ``qparams`` vector on one device, immutable.  A subclass lists its slots in its constructor's order, says in
+    TAKES what the constructor takes and in MADE_BY where such an object comes from, sets QDTYPE, and gives
+    ``_set`` its shape rule and the length of its qparams."""
+    __slots__ = ()
+    QDTYPE = torch.float64
+
+    def _set(self, tensors, coef_form, coef_ok, nq, then=None):
+        """Check and store the tensors (name -> tensor, coef first, qparams last); ``then`` checks what a subclass
+        holds besides, once coef is known to be sound."""
+        coef, qparams = tensors["coef"], tensors["qparams"]
+        if not all(torch.is_tensor(t) for t in tensors.values()):
+            raise ValueError(f"{type(self).__name__} takes {self.TAKES}")
+        if coef.dtype != torch.uint8 or coef.numel() == 0 or not coef.is_contiguous() or not coef_ok(coef):
+            raise ValueError(f"coef must be a contiguous uint8 {coef_form} tensor; got {coef.dtype} "
+                             f"{tuple(coef.shape)}")
+        if then is not None:
+            then()
+        if qparams.dtype != self.QDTYPE or tuple(qparams.shape) != (nq,) or not qparams.is_contiguous():
+            raise ValueError(f"qparams must be a contiguous {_dtype_name(self.QDTYPE)} [{nq}] tensor; got "
+                             f"{qparams.dtype} {tuple(qparams.shape)}")
+        if len({t.device for t in tensors.values()}) != 1:
+            names = list(tensors)
+            raise ValueError(f"{', '.join(names[:-1])} and {names[-1]} must be on one device; got "
+                             f"{', '.join(str(t.device) for t in tensors.values())}")
+        for name, t in tensors.items():
+            object.__setattr__(self, "_" + name, t)
+
+    def __setattr__(self, name, value):
+        raise AttributeError(f"{type(self).__name__} is immutable")
+
+    coef = property(lambda self: self._coef)
+    qparams = property(lambda self: self._qparams)
+    device = property(lambda self: self._coef.device)
+
+    def _host(self):
+        return self._qparams.detach().cpu().numpy()
+
+    def _args(self):
+        return tuple(getattr(self, slot) for slot in self.__slots__)
+
+    def to(self, device):
+        return type(self)(*(a.to(device) if torch.is_tensor(a) else a for a in self._args()))
+
+    def _file_qparams(self):
+        """qparams on the host with the six scales rounded to the nine significant digits of a .ptm header."""
+        qp = self._host().copy()
+        qp[:6] = [float("%.9g" % x) for x in qp[:6]]
+        return qp
+
+    def _with_qparams(self, qp):
+        """The same bytes with the host array qp for qparams."""
+        return type(self)(*(torch.as_tensor(qp).to(self.device) if a is self._qparams else a for a in self._args()))
+
+
+def _dtype_name(dtype):
+    return str(dtype).replace("torch.", "")
+
+
+def _quantised(q, cls, name="q"):
+    """q must be a cls on the GPU."""
+    if not isinstance(q, cls):
+        raise ValueError(f"{name} must be a {cls.__name__} ({cls.MADE_BY}); got {type(q).__name__}")
+    _require_cuda(q.coef, f"{name}.coef")
+
+
+def _bytes_map(coef8, nbytes, what):
+    """A contiguous CUDA uint8 map of nbytes per pixel (``what`` in words) -> P."""
+    _require_cuda(coef8, "coef8")
+    if coef8.dtype != torch.uint8 or not coef8.is_contiguous() or coef8.numel() == 0 or coef8.numel() % nbytes:
+        raise ValueError(f"coef8 must be a contiguous uint8 map of {what} per pixel; got {coef8.dtype} "
+                         f"{tuple(coef8.shape)}")
+    return coef8.numel() // nbytes
+
+
+def _qparams_arg(qparams, dtype, n, like):
+    _require_cuda(qparams, "qparams")
+    if qparams.dtype != dtype or qparams.numel() != n or not qparams.is_contiguous() or qparams.device != like.device:
+        raise ValueError(f"qparams must be a contiguous {_dtype_name(dtype)} [{n}] tensor on {like.device}; got "
+                         f"{qparams.dtype} {tuple(qparams.shape)} on {qparams.device}")
+    return _vp(qparams)
+
+
+def _workspace_bytes(n, P):
+    """What a ``rti_*_qparams_workspace`` query returned -> the bytes, or P was not positive."""
+    if n <= 0:
+        raise ValueError(f"P must be positive; got {P}")
+    return int(n)
+
+
+def _workspace_arg(workspace, need, like):
+    _require_cuda(workspace, "workspace")
+    if not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need \
+            or workspace.device != like.device:
+        raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on {like.device}; got "
+                         f"{workspace.numel() * workspace.element_size()} bytes on {workspace.device}")
+    return _vp(workspace)
+
+
+def _luv_arg(luv_dev, like):
+    """CUDA fp64 [E, 2] on like's device -> (pointer, E)."""
+    _require_cuda(luv_dev, "luv")
+    if luv_dev.dtype != torch.float64 or luv_dev.dim() != 2 or luv_dev.shape[1] != 2 or luv_dev.shape[0] < 1 \
+            or not luv_dev.is_contiguous() or luv_dev.device != like.device:
+        raise ValueError(f"luv must be a contiguous float64 [E, 2] tensor on {like.device}; got {luv_dev.dtype} "
+                         f"{tuple(luv_dev.shape)} on {luv_dev.device}")
+    return _vp(luv_dev), luv_dev.shape[0]
+
+
+def _out8_dtype(out):
+    odt = _ENHANCED_DTYPES.get(out.dtype) if torch.is_tensor(out) else None
+    if odt is None:
+        raise ValueError("out must be a float32, int32 or uint8 tensor")
+    return odt
+
+
+def _relight8(q, lu, lv, out_dtype, launch):
+    """What ``relight_lrgb8``, ``relight_hsh8`` and ``relight_rgb8`` do around their launch(luv_dev, out)."""
+    if out_dtype not in _ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    scalar = np.ndim(lu) == 0 and np.ndim(lv) == 0
+    luv = np.stack([np.asarray(lu, np.float64).ravel(), np.asarray(lv, np.float64).ravel()], -1)
+    luv_d = torch.as_tensor(np.ascontiguousarray(luv), device=q.device)
+    out = torch.empty((luv.shape[0],) + q.shape + (3,), dtype=out_dtype, device=q.device)
+    launch(luv_d, out)
+    return out[0] if scalar else out
+
+
 # ---- 8-bit LRGB PTMs: the .ptm payload on the device (rti_lrgb8.hip, DESIGN.md §4.8) ---------
 
-class QuantisedLRGB:
+class QuantisedLRGB(_Quantised):
     """An 8-bit LRGB PTM: the two blocks of a ``PTM_FORMAT_LRGB`` payload and its header values.
 
     coef: uint8 [H, W, 6] or [P, 6], the bytes a0..a5 per pixel; rgb: uint8 [..., 3]; qparams: fp64 [13] =
@@ -1334,82 +1465,39 @@ class QuantisedLRGB:
     ``read_ptm(path, quantised=True)``); immutable.  ``scale`` / ``bias`` / ``s`` copy qparams to the host: they
     are the one accessor that synchronises."""
     __slots__ = ("_coef", "_rgb", "_qparams")
+    TAKES = "three tensors (coef, rgb, qparams)"
+    MADE_BY = "quantise_lrgb, or read_ptm(path, quantised=True)"
 
     def __init__(self, coef, rgb, qparams):
-        if not (torch.is_tensor(coef) and torch.is_tensor(rgb) and torch.is_tensor(qparams)):
-            raise ValueError("QuantisedLRGB takes three tensors (coef, rgb, qparams)")
-        if coef.dtype != torch.uint8 or coef.dim() < 2 or coef.shape[-1] != 6 or coef.numel() == 0 \
-                or not coef.is_contiguous():
-            raise ValueError(f"coef must be a contiguous uint8 [..., 6] tensor; got {coef.dtype} {tuple(coef.shape)}")
-        if rgb.dtype != torch.uint8 or tuple(rgb.shape) != tuple(coef.shape[:-1]) + (3,) or not rgb.is_contiguous():
-            raise ValueError(f"rgb must be a contiguous uint8 {tuple(coef.shape[:-1]) + (3,)} tensor; got "
-                             f"{rgb.dtype} {tuple(rgb.shape)}")
-        if qparams.dtype != torch.float64 or tuple(qparams.shape) != (13,) or not qparams.is_contiguous():
-            raise ValueError(f"qparams must be a contiguous float64 [13] tensor; got {qparams.dtype} "
-                             f"{tuple(qparams.shape)}")
-        if not coef.device == rgb.device == qparams.device:
-            raise ValueError(f"coef, rgb and qparams must be on one device; got {coef.device}, {rgb.device}, "
-                             f"{qparams.device}")
-        for name, v in zip(self.__slots__, (coef, rgb, qparams)):
-            object.__setattr__(self, name, v)
+        def rgb_block():
+            want = tuple(coef.shape[:-1]) + (3,)
+            if rgb.dtype != torch.uint8 or tuple(rgb.shape) != want or not rgb.is_contiguous():
+                raise ValueError(f"rgb must be a contiguous uint8 {want} tensor; got {rgb.dtype} {tuple(rgb.shape)}")
+        self._set({"coef": coef, "rgb": rgb, "qparams": qparams}, "[..., 6]",
+                  lambda c: c.dim() >= 2 and c.shape[-1] == 6, 13, rgb_block)
 
-    def __setattr__(self, name, value):
-        raise AttributeError("QuantisedLRGB is immutable")
-
-    coef = property(lambda self: self._coef)
     rgb = property(lambda self: self._rgb)
-    qparams = property(lambda self: self._qparams)
     shape = property(lambda self: tuple(self._coef.shape[:-1]), doc="the spatial shape: (H, W) or (P,)")
-    device = property(lambda self: self._coef.device)
-
-    def _host(self):
-        return self._qparams.detach().cpu().numpy()
-
     scale = property(lambda self: self._host()[:6].copy(), doc="host fp64 [6] (synchronises)")
     bias = property(lambda self: self._host()[6:12].copy(), doc="host fp64 [6], integral values (synchronises)")
     s = property(lambda self: float(self._host()[12]), doc="the chroma scale, a host float (synchronises)")
-
-    def to(self, device):
-        return QuantisedLRGB(self._coef.to(device), self._rgb.to(device), self._qparams.to(device))
 
     def with_file_scales(self):
         """The map as a .ptm round trip yields it: the same bytes, the scales rounded to the nine significant
         digits ``write_ptm`` puts in the header, s = 1.  ``quantise_lrgb`` keeps the full fp64 scales the bytes
         were made with; a file does not, so ``dequantise_lrgb`` / ``relight_lrgb8`` of this map, not of the fresh
         one, equal ``read_ptm`` of the written file to the bit.  Synchronises."""
-        qp = self._host().copy()
-        qp[:6] = [float("%.9g" % x) for x in qp[:6]]
+        qp = self._file_qparams()
         qp[12] = 1.0
-        return QuantisedLRGB(self._coef, self._rgb, torch.as_tensor(qp).to(self.device))
+        return self._with_qparams(qp)
 
     def __repr__(self):
         return f"QuantisedLRGB(shape={self.shape}, device={self.device})"
 
 
-def _quantised(q, name="q"):
-    """A QuantisedLRGB on the GPU -> P."""
-    if not isinstance(q, QuantisedLRGB):
-        raise ValueError(f"{name} must be a QuantisedLRGB (quantise_lrgb, or read_ptm(path, quantised=True)); got "
-                         f"{type(q).__name__}")
-    _require_cuda(q.coef, f"{name}.coef")
-    return q.coef.numel() // 6
-
-
-def _qparams_dev(qparams, like):
-    _require_cuda(qparams, "qparams")
-    if qparams.dtype != torch.float64 or qparams.numel() != 13 or not qparams.is_contiguous() \
-            or qparams.device != like.device:
-        raise ValueError(f"qparams must be a contiguous float64 [13] tensor on {like.device}; got {qparams.dtype} "
-                         f"{tuple(qparams.shape)} on {qparams.device}")
-    return _vp(qparams)
-
-
 def lrgb_qparams_workspace(P):
     """Bytes of device scratch ``lrgb_qparams_into`` needs for P pixels (``rti_lrgb_qparams_workspace``)."""
-    n = int(L.lib().rti_lrgb_qparams_workspace(int(P)))
-    if n <= 0:
-        raise ValueError(f"P must be positive; got {P}")
-    return n
+    return _workspace_bytes(L.lib().rti_lrgb_qparams_workspace(int(P)), P)
 
 
 def lrgb_qparams_into(lrgb, workspace, qparams, *, layout="pixel"):
@@ -1420,13 +1508,8 @@ def lrgb_qparams_into(lrgb, workspace, qparams, *, layout="pixel"):
     contiguous CUDA tensor of at least ``lrgb_qparams_workspace(P)`` bytes (it need not be initialised);
     qparams: CUDA fp64 [13]."""
     P = _lrgb_map(lrgb)
-    _require_cuda(workspace, "workspace")
-    need = lrgb_qparams_workspace(P)
-    if not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need \
-            or workspace.device != lrgb.device:
-        raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on {lrgb.device}; got "
-                         f"{workspace.numel() * workspace.element_size()} bytes on {workspace.device}")
-    st = L.lib().rti_lrgb_qparams(_vp(lrgb), _layout_id(layout), P, _vp(workspace), _qparams_dev(qparams, lrgb),
+    ws = _workspace_arg(workspace, lrgb_qparams_workspace(P), lrgb)
+    st = L.lib().rti_lrgb_qparams(_vp(lrgb), _layout_id(layout), P, ws, _qparams_arg(qparams, torch.float64, 13, lrgb),
                                   _stream_of(lrgb))
     L.check(st, "rti_lrgb_qparams")
     return qparams
@@ -1438,7 +1521,7 @@ def lrgb_quantise_into(lrgb, qparams, coef8, rgb8, *, layout="pixel"):
     lrgb: as ``lrgb_qparams_into``; qparams: CUDA fp64 [13] (``lrgb_qparams_into``); coef8: uint8 with 6·P
     elements ([P, 6]); rgb8: uint8 with 3·P elements ([P, 3]).  Returns (coef8, rgb8)."""
     P = _lrgb_map(lrgb)
-    st = L.lib().rti_lrgb_quantise(_vp(lrgb), _layout_id(layout), P, _qparams_dev(qparams, lrgb),
+    st = L.lib().rti_lrgb_quantise(_vp(lrgb), _layout_id(layout), P, _qparams_arg(qparams, torch.float64, 13, lrgb),
                                    _map_out(coef8, "coef8", torch.uint8, 6 * P, lrgb),
                                    _map_out(rgb8, "rgb8", torch.uint8, 3 * P, lrgb), _stream_of(lrgb))
     L.check(st, "rti_lrgb_quantise")
@@ -1483,25 +1566,14 @@ def relight_lrgb8_into(coef8, rgb8, qparams, luv_dev, out):
 
     coef8: contiguous CUDA uint8 [P, 6], any spatial shape in place of P; rgb8: uint8 [P, 3]; qparams: CUDA fp64
     [13]; luv_dev: CUDA fp64 [E, 2]; out: float32, int32 or uint8 with E·P·3 elements ([E, P, 3])."""
-    _require_cuda(coef8, "coef8")
-    if coef8.dtype != torch.uint8 or not coef8.is_contiguous() or coef8.numel() == 0 or coef8.numel() % 6:
-        raise ValueError(f"coef8 must be a contiguous uint8 map of 6 bytes per pixel; got {coef8.dtype} "
-                         f"{tuple(coef8.shape)}")
-    P = coef8.numel() // 6
+    P = _bytes_map(coef8, 6, "6 bytes")
     _require_cuda(rgb8, "rgb8")
     if rgb8.dtype != torch.uint8 or not rgb8.is_contiguous() or rgb8.numel() != 3 * P or rgb8.device != coef8.device:
         raise ValueError(f"rgb8 must be a contiguous uint8 tensor of {3 * P} elements on {coef8.device}; got "
                          f"{rgb8.dtype} {tuple(rgb8.shape)} on {rgb8.device}")
-    _require_cuda(luv_dev, "luv")
-    if luv_dev.dtype != torch.float64 or luv_dev.dim() != 2 or luv_dev.shape[1] != 2 or luv_dev.shape[0] < 1 \
-            or not luv_dev.is_contiguous() or luv_dev.device != coef8.device:
-        raise ValueError(f"luv must be a contiguous float64 [E, 2] tensor on {coef8.device}; got {luv_dev.dtype} "
-                         f"{tuple(luv_dev.shape)} on {luv_dev.device}")
-    E = luv_dev.shape[0]
-    odt = _ENHANCED_DTYPES.get(out.dtype) if torch.is_tensor(out) else None
-    if odt is None:
-        raise ValueError("out must be a float32, int32 or uint8 tensor")
-    st = L.lib().rti_relight_lrgb8(_vp(coef8), _vp(rgb8), P, _qparams_dev(qparams, coef8), _vp(luv_dev), E,
+    luv, E = _luv_arg(luv_dev, coef8)
+    odt = _out8_dtype(out)
+    st = L.lib().rti_relight_lrgb8(_vp(coef8), _vp(rgb8), P, _qparams_arg(qparams, torch.float64, 13, coef8), luv, E,
                                    _map_out(out, "out", out.dtype, E * P * 3, coef8), odt, _stream_of(coef8))
     L.check(st, "rti_relight_lrgb8")
     return out
@@ -1514,15 +1586,9 @@ def relight_lrgb8(q, lu, lv, *, out_dtype=torch.float32):
 
     q: a ``QuantisedLRGB`` on the GPU.  lu, lv: scalars or E directions.  Returns [E, H, W, 3], squeezed to
     [H, W, 3] for scalar directions, in out_dtype: float32, or int32 / uint8 converted as ``relight`` does."""
-    _quantised(q)
-    if out_dtype not in _ENHANCED_DTYPES:
-        raise ValueError("out_dtype must be float32, int32 or uint8")
-    scalar = np.ndim(lu) == 0 and np.ndim(lv) == 0
-    luv = np.stack([np.asarray(lu, np.float64).ravel(), np.asarray(lv, np.float64).ravel()], -1)
-    luv_d = torch.as_tensor(np.ascontiguousarray(luv), device=q.device)
-    out = torch.empty((luv.shape[0],) + q.shape + (3,), dtype=out_dtype, device=q.device)
-    relight_lrgb8_into(q.coef, q.rgb, q.qparams, luv_d, out)
-    return out[0] if scalar else out
+    _quantised(q, QuantisedLRGB)
+    return _relight8(q, lu, lv, out_dtype,
+                     lambda luv_d, out: relight_lrgb8_into(q.coef, q.rgb, q.qparams, luv_d, out))
 
 
 # ---- 8-bit RGB HSH maps: the .rti payload on the device (rti_hsh8.hip, DESIGN.md §4.9) -------
@@ -1539,7 +1605,7 @@ def _hsh8_basis(basis):
     return b
 
 
-class QuantisedHSH:
+class QuantisedHSH(_Quantised):
     """An 8-bit RGB HSH map: the payload of an HSH ``.rti`` file and its header values.
 
     coef: uint8 [H, W, 3, k] or [P, 3, k], per pixel the k bytes of R, then G, then B; qparams: fp32 [2k] =
@@ -1548,42 +1614,22 @@ class QuantisedHSH:
     device (the GPU, or the host for ``read_rti(path, quantised=True)``); immutable.  ``scale`` / ``bias`` copy
     qparams to the host: they are the one accessor that synchronises."""
     __slots__ = ("_coef", "_qparams", "_basis")
+    TAKES = "two tensors (coef, qparams) and a basis"
+    MADE_BY = "quantise_hsh, or read_rti(path, quantised=True)"
+    QDTYPE = torch.float32
 
     def __init__(self, coef, qparams, basis):
         b = _hsh8_basis(basis)
         k = _HSH8_TERMS[b]
-        if not (torch.is_tensor(coef) and torch.is_tensor(qparams)):
-            raise ValueError("QuantisedHSH takes two tensors (coef, qparams) and a basis")
-        if coef.dtype != torch.uint8 or coef.dim() < 3 or tuple(coef.shape[-2:]) != (3, k) or coef.numel() == 0 \
-                or not coef.is_contiguous():
-            raise ValueError(f"coef must be a contiguous uint8 [..., 3, {k}] tensor; got {coef.dtype} "
-                             f"{tuple(coef.shape)}")
-        if qparams.dtype != torch.float32 or tuple(qparams.shape) != (2 * k,) or not qparams.is_contiguous():
-            raise ValueError(f"qparams must be a contiguous float32 [{2 * k}] tensor; got {qparams.dtype} "
-                             f"{tuple(qparams.shape)}")
-        if coef.device != qparams.device:
-            raise ValueError(f"coef and qparams must be on one device; got {coef.device}, {qparams.device}")
-        for name, v in zip(self.__slots__, (coef, qparams, b)):
-            object.__setattr__(self, name, v)
+        self._set({"coef": coef, "qparams": qparams}, f"[..., 3, {k}]",
+                  lambda c: c.dim() >= 3 and tuple(c.shape[-2:]) == (3, k), 2 * k)
+        object.__setattr__(self, "_basis", b)
 
-    def __setattr__(self, name, value):
-        raise AttributeError("QuantisedHSH is immutable")
-
-    coef = property(lambda self: self._coef)
-    qparams = property(lambda self: self._qparams)
     basis = property(lambda self: _HSH8_NAMES[self._basis], doc='"hsh9" or "hsh16"')
     k = property(lambda self: _HSH8_TERMS[self._basis], doc="terms per channel: 9 or 16")
     shape = property(lambda self: tuple(self._coef.shape[:-2]), doc="the spatial shape: (H, W) or (P,)")
-    device = property(lambda self: self._coef.device)
-
-    def _host(self):
-        return self._qparams.detach().cpu().numpy()
-
     scale = property(lambda self: self._host()[:self.k].copy(), doc="host fp32 [k] (synchronises)")
     bias = property(lambda self: self._host()[self.k:].copy(), doc="host fp32 [k] (synchronises)")
-
-    def to(self, device):
-        return QuantisedHSH(self._coef.to(device), self._qparams.to(device), self._basis)
 
     def __repr__(self):
         return f"QuantisedHSH(shape={self.shape}, basis={self.basis!r}, device={self.device})"
@@ -1599,21 +1645,9 @@ def _hsh_maps(coef, k):
     return coef.numel() // (3 * k)
 
 
-def _hsh_qparams_dev(qparams, k, like):
-    _require_cuda(qparams, "qparams")
-    if qparams.dtype != torch.float32 or qparams.numel() != 2 * k or not qparams.is_contiguous() \
-            or qparams.device != like.device:
-        raise ValueError(f"qparams must be a contiguous float32 [{2 * k}] tensor on {like.device}; got "
-                         f"{qparams.dtype} {tuple(qparams.shape)} on {qparams.device}")
-    return _vp(qparams)
-
-
 def hsh_qparams_workspace(P, basis="hsh16"):
     """Bytes of device scratch ``hsh_qparams_into`` needs for P pixels (``rti_hsh_qparams_workspace``)."""
-    n = int(L.lib().rti_hsh_qparams_workspace(_HSH8_TERMS[_hsh8_basis(basis)], int(P)))
-    if n <= 0:
-        raise ValueError(f"P must be positive; got {P}")
-    return n
+    return _workspace_bytes(L.lib().rti_hsh_qparams_workspace(_HSH8_TERMS[_hsh8_basis(basis)], int(P)), P)
 
 
 def hsh_qparams_into(coef, workspace, qparams, *, basis="hsh16", layout="pixel"):
@@ -1626,14 +1660,9 @@ def hsh_qparams_into(coef, workspace, qparams, *, basis="hsh16", layout="pixel")
     b = _hsh8_basis(basis)
     k = _HSH8_TERMS[b]
     P = _hsh_maps(coef, k)
-    _require_cuda(workspace, "workspace")
-    need = hsh_qparams_workspace(P, b)
-    if not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need \
-            or workspace.device != coef.device:
-        raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on {coef.device}; got "
-                         f"{workspace.numel() * workspace.element_size()} bytes on {workspace.device}")
-    st = L.lib().rti_hsh_qparams(_vp(coef), b, _layout_id(layout), 0, P, _vp(workspace),
-                                 _hsh_qparams_dev(qparams, k, coef), _stream_of(coef))
+    ws = _workspace_arg(workspace, hsh_qparams_workspace(P, b), coef)
+    st = L.lib().rti_hsh_qparams(_vp(coef), b, _layout_id(layout), 0, P, ws,
+                                 _qparams_arg(qparams, torch.float32, 2 * k, coef), _stream_of(coef))
     L.check(st, "rti_hsh_qparams")
     return qparams
 
@@ -1646,7 +1675,8 @@ def hsh_quantise_into(coef, qparams, coef8, *, basis="hsh16", layout="pixel"):
     b = _hsh8_basis(basis)
     k = _HSH8_TERMS[b]
     P = _hsh_maps(coef, k)
-    st = L.lib().rti_hsh_quantise(_vp(coef), b, _layout_id(layout), 0, P, _hsh_qparams_dev(qparams, k, coef),
+    st = L.lib().rti_hsh_quantise(_vp(coef), b, _layout_id(layout), 0, P,
+                                  _qparams_arg(qparams, torch.float32, 2 * k, coef),
                                   _map_out(coef8, "coef8", torch.uint8, 3 * k * P, coef), _stream_of(coef))
     L.check(st, "rti_hsh_quantise")
     return coef8
@@ -1700,21 +1730,10 @@ def relight_hsh8_into(coef8, qparams, luv_dev, out, *, basis="hsh16"):
     CUDA fp64 [E, 2]; out: float32, int32 or uint8 with E·P·3 elements ([E, P, 3])."""
     b = _hsh8_basis(basis)
     k = _HSH8_TERMS[b]
-    _require_cuda(coef8, "coef8")
-    if coef8.dtype != torch.uint8 or not coef8.is_contiguous() or coef8.numel() == 0 or coef8.numel() % (3 * k):
-        raise ValueError(f"coef8 must be a contiguous uint8 map of {3 * k} bytes per pixel; got {coef8.dtype} "
-                         f"{tuple(coef8.shape)}")
-    P = coef8.numel() // (3 * k)
-    _require_cuda(luv_dev, "luv")
-    if luv_dev.dtype != torch.float64 or luv_dev.dim() != 2 or luv_dev.shape[1] != 2 or luv_dev.shape[0] < 1 \
-            or not luv_dev.is_contiguous() or luv_dev.device != coef8.device:
-        raise ValueError(f"luv must be a contiguous float64 [E, 2] tensor on {coef8.device}; got {luv_dev.dtype} "
-                         f"{tuple(luv_dev.shape)} on {luv_dev.device}")
-    E = luv_dev.shape[0]
-    odt = _ENHANCED_DTYPES.get(out.dtype) if torch.is_tensor(out) else None
-    if odt is None:
-        raise ValueError("out must be a float32, int32 or uint8 tensor")
-    st = L.lib().rti_relight_hsh8(_vp(coef8), b, P, _hsh_qparams_dev(qparams, k, coef8), _vp(luv_dev), E,
+    P = _bytes_map(coef8, 3 * k, f"{3 * k} bytes")
+    luv, E = _luv_arg(luv_dev, coef8)
+    odt = _out8_dtype(out)
+    st = L.lib().rti_relight_hsh8(_vp(coef8), b, P, _qparams_arg(qparams, torch.float32, 2 * k, coef8), luv, E,
                                   _map_out(out, "out", out.dtype, E * P * 3, coef8), odt, _stream_of(coef8))
     L.check(st, "rti_relight_hsh8")
     return out
@@ -1727,18 +1746,9 @@ def relight_hsh8(q, lu, lv, *, out_dtype=torch.float32):
 
     q: a ``QuantisedHSH`` on the GPU.  lu, lv: scalars or E directions.  Returns [E, H, W, 3], squeezed to
     [H, W, 3] for scalar directions, in out_dtype: float32, or int32 / uint8 converted as ``relight`` does."""
-    if not isinstance(q, QuantisedHSH):
-        raise ValueError(f"q must be a QuantisedHSH (quantise_hsh, or read_rti(path, quantised=True)); got "
-                         f"{type(q).__name__}")
-    _require_cuda(q.coef, "q.coef")
-    if out_dtype not in _ENHANCED_DTYPES:
-        raise ValueError("out_dtype must be float32, int32 or uint8")
-    scalar = np.ndim(lu) == 0 and np.ndim(lv) == 0
-    luv = np.stack([np.asarray(lu, np.float64).ravel(), np.asarray(lv, np.float64).ravel()], -1)
-    luv_d = torch.as_tensor(np.ascontiguousarray(luv), device=q.device)
-    out = torch.empty((luv.shape[0],) + q.shape + (3,), dtype=out_dtype, device=q.device)
-    relight_hsh8_into(q.coef, q.qparams, luv_d, out, basis=q._basis)
-    return out[0] if scalar else out
+    _quantised(q, QuantisedHSH)
+    return _relight8(q, lu, lv, out_dtype,
+                     lambda luv_d, out: relight_hsh8_into(q.coef, q.qparams, luv_d, out, basis=q._basis))
 
 
 # ---- HSH surface normals: a peak-direction search (rti_hsh_normals.hip, DESIGN.md §4.10) ------
@@ -1838,12 +1848,9 @@ def hsh8_normals_into(coef8, qparams, table, normals, kind=None, peak=None, *, b
     ``hsh_normals_into``."""
     b = _hsh8_basis(basis)
     k = _HSH8_TERMS[b]
-    _require_cuda(coef8, "coef8")
-    if coef8.dtype != torch.uint8 or not coef8.is_contiguous() or coef8.numel() == 0 or coef8.numel() % (3 * k):
-        raise ValueError(f"coef8 must be a contiguous uint8 map of {3 * k} bytes per pixel; got {coef8.dtype} "
-                         f"{tuple(coef8.shape)}")
-    P = coef8.numel() // (3 * k)
-    st = L.lib().rti_hsh8_normals(_vp(coef8), b, P, _hsh_qparams_dev(qparams, k, coef8), _luma_weights(weights),
+    P = _bytes_map(coef8, 3 * k, f"{3 * k} bytes")
+    st = L.lib().rti_hsh8_normals(_vp(coef8), b, P, _qparams_arg(qparams, torch.float32, 2 * k, coef8),
+                                  _luma_weights(weights),
                                   int(grid), _peak_table_arg(table, b, grid, coef8),
                                   _map_out(normals, "normals", torch.float32, 3 * P, coef8),
                                   _normal_layout_id(normal_layout),
@@ -1905,10 +1912,7 @@ def hsh8_normals(q, *, normal_layout="pixel", grid=10, weights=None, return_kind
     ``hsh_normals(dequantise_hsh(q), q.basis, ...)`` bit for bit, without the fp32 maps.
 
     q: a ``QuantisedHSH`` on the GPU.  Returns what ``hsh_normals`` returns."""
-    if not isinstance(q, QuantisedHSH):
-        raise ValueError(f"q must be a QuantisedHSH (quantise_hsh, or read_rti(path, quantised=True)); got "
-                         f"{type(q).__name__}")
-    _require_cuda(q.coef, "q.coef")
+    _quantised(q, QuantisedHSH)
     nl = _normal_layout_id(normal_layout)
     n, kind, peak = _normal_outputs(q.shape, nl, return_kind, return_peak, q.device)
     hsh8_normals_into(q.coef, q.qparams, peak_table(q._basis, grid, q.device), n, kind, peak, basis=q._basis,
@@ -1918,7 +1922,7 @@ def hsh8_normals(q, *, normal_layout="pixel", grid=10, weights=None, return_kind
 
 # ---- 8-bit RGB PTMs: the PTM_FORMAT_RGB payload on the device (rti_rgb8.hip) --
 
-class QuantisedRGB:
+class QuantisedRGB(_Quantised):
     """An 8-bit RGB PTM: the three coefficient blocks of a ``PTM_FORMAT_RGB`` payload and its header values.
 
     coef: uint8 [3, H, W, 6] or [3, P, 6]: block R, then G, then B, each the bytes a0..a5 per pixel; qparams: fp64
@@ -1927,58 +1931,26 @@ class QuantisedRGB:
     GPU, or the host for ``read_ptm8``); immutable.  ``scale`` / ``bias`` copy qparams to the host: they are the
     one accessor that synchronises."""
     __slots__ = ("_coef", "_qparams")
+    TAKES = "two tensors (coef, qparams)"
+    MADE_BY = "quantise_rgb, or read_ptm8(path)"
 
     def __init__(self, coef, qparams):
-        if not (torch.is_tensor(coef) and torch.is_tensor(qparams)):
-            raise ValueError("QuantisedRGB takes two tensors (coef, qparams)")
-        if coef.dtype != torch.uint8 or coef.dim() < 3 or coef.shape[0] != 3 or coef.shape[-1] != 6 \
-                or coef.numel() == 0 or not coef.is_contiguous():
-            raise ValueError(f"coef must be a contiguous uint8 [3, ..., 6] tensor; got {coef.dtype} "
-                             f"{tuple(coef.shape)}")
-        if qparams.dtype != torch.float64 or tuple(qparams.shape) != (12,) or not qparams.is_contiguous():
-            raise ValueError(f"qparams must be a contiguous float64 [12] tensor; got {qparams.dtype} "
-                             f"{tuple(qparams.shape)}")
-        if coef.device != qparams.device:
-            raise ValueError(f"coef and qparams must be on one device; got {coef.device}, {qparams.device}")
-        for name, v in zip(self.__slots__, (coef, qparams)):
-            object.__setattr__(self, name, v)
+        self._set({"coef": coef, "qparams": qparams}, "[3, ..., 6]",
+                  lambda c: c.dim() >= 3 and c.shape[0] == 3 and c.shape[-1] == 6, 12)
 
-    def __setattr__(self, name, value):
-        raise AttributeError("QuantisedRGB is immutable")
-
-    coef = property(lambda self: self._coef)
-    qparams = property(lambda self: self._qparams)
     shape = property(lambda self: tuple(self._coef.shape[1:-1]), doc="the spatial shape: (H, W) or (P,)")
-    device = property(lambda self: self._coef.device)
-
-    def _host(self):
-        return self._qparams.detach().cpu().numpy()
-
     scale = property(lambda self: self._host()[:6].copy(), doc="host fp64 [6] (synchronises)")
     bias = property(lambda self: self._host()[6:].copy(), doc="host fp64 [6], integral values (synchronises)")
-
-    def to(self, device):
-        return QuantisedRGB(self._coef.to(device), self._qparams.to(device))
 
     def with_file_scales(self):
         """The map as a .ptm round trip yields it: the same bytes, the scales rounded to the nine significant
         digits ``write_ptm`` puts in the header.  ``quantise_rgb`` keeps the full fp64 scales the bytes were made
         with; a file does not, so ``dequantise_rgb`` / ``relight_rgb8`` / ``rgb8_normals`` of this map, not of the
         fresh one, equal those of the written file to the bit.  Synchronises."""
-        qp = self._host().copy()
-        qp[:6] = [float("%.9g" % x) for x in qp[:6]]
-        return QuantisedRGB(self._coef, torch.as_tensor(qp).to(self.device))
+        return self._with_qparams(self._file_qparams())
 
     def __repr__(self):
         return f"QuantisedRGB(shape={self.shape}, device={self.device})"
-
-
-def _quantised_rgb(q, name="q"):
-    """A QuantisedRGB on the GPU -> P."""
-    if not isinstance(q, QuantisedRGB):
-        raise ValueError(f"{name} must be a QuantisedRGB (quantise_rgb, or read_ptm8(path)); got {type(q).__name__}")
-    _require_cuda(q.coef, f"{name}.coef")
-    return q.coef.numel() // 18
 
 
 def _rgb_maps(coef):
@@ -1991,30 +1963,9 @@ def _rgb_maps(coef):
     return coef.numel() // 18
 
 
-def _rgb8_qparams_dev(qparams, like):
-    _require_cuda(qparams, "qparams")
-    if qparams.dtype != torch.float64 or qparams.numel() != 12 or not qparams.is_contiguous() \
-            or qparams.device != like.device:
-        raise ValueError(f"qparams must be a contiguous float64 [12] tensor on {like.device}; got {qparams.dtype} "
-                         f"{tuple(qparams.shape)} on {qparams.device}")
-    return _vp(qparams)
-
-
-def _rgb8_bytes(coef8):
-    """A contiguous CUDA uint8 map of three blocks of 6 bytes per pixel -> P."""
-    _require_cuda(coef8, "coef8")
-    if coef8.dtype != torch.uint8 or not coef8.is_contiguous() or coef8.numel() == 0 or coef8.numel() % 18:
-        raise ValueError(f"coef8 must be a contiguous uint8 map of three blocks of 6 bytes per pixel; got "
-                         f"{coef8.dtype} {tuple(coef8.shape)}")
-    return coef8.numel() // 18
-
-
 def rgb8_qparams_workspace(P):
     """Bytes of device scratch ``rgb8_qparams_into`` needs for P pixels (``rti_rgb8_qparams_workspace``)."""
-    n = int(L.lib().rti_rgb8_qparams_workspace(int(P)))
-    if n <= 0:
-        raise ValueError(f"P must be positive; got {P}")
-    return n
+    return _workspace_bytes(L.lib().rti_rgb8_qparams_workspace(int(P)), P)
 
 
 def rgb8_qparams_into(coef, workspace, qparams, *, layout="pixel"):
@@ -2025,14 +1976,9 @@ def rgb8_qparams_into(coef, workspace, qparams, *, layout="pixel"):
     P; workspace: a contiguous CUDA tensor of at least ``rgb8_qparams_workspace(P)`` bytes (it need not be
     initialised); qparams: CUDA fp64 [12]."""
     P = _rgb_maps(coef)
-    _require_cuda(workspace, "workspace")
-    need = rgb8_qparams_workspace(P)
-    if not workspace.is_contiguous() or workspace.numel() * workspace.element_size() < need \
-            or workspace.device != coef.device:
-        raise ValueError(f"workspace must be a contiguous tensor of at least {need} bytes on {coef.device}; got "
-                         f"{workspace.numel() * workspace.element_size()} bytes on {workspace.device}")
-    st = L.lib().rti_rgb8_qparams(_vp(coef), _layout_id(layout), 0, P, _vp(workspace),
-                                  _rgb8_qparams_dev(qparams, coef), _stream_of(coef))
+    ws = _workspace_arg(workspace, rgb8_qparams_workspace(P), coef)
+    st = L.lib().rti_rgb8_qparams(_vp(coef), _layout_id(layout), 0, P, ws,
+                                  _qparams_arg(qparams, torch.float64, 12, coef), _stream_of(coef))
     L.check(st, "rti_rgb8_qparams")
     return qparams
 
@@ -2043,7 +1989,7 @@ def rgb8_quantise_into(coef, qparams, coef8, *, layout="pixel"):
     coef: as ``rgb8_qparams_into``; qparams: CUDA fp64 [12] (``rgb8_qparams_into``); coef8: uint8 with 18·P
     elements ([3, P, 6]).  Returns coef8."""
     P = _rgb_maps(coef)
-    st = L.lib().rti_rgb8_quantise(_vp(coef), _layout_id(layout), 0, P, _rgb8_qparams_dev(qparams, coef),
+    st = L.lib().rti_rgb8_quantise(_vp(coef), _layout_id(layout), 0, P, _qparams_arg(qparams, torch.float64, 12, coef),
                                    _map_out(coef8, "coef8", torch.uint8, 18 * P, coef), _stream_of(coef))
     L.check(st, "rti_rgb8_quantise")
     return coef8
@@ -2087,17 +2033,10 @@ def relight_rgb8_into(coef8, qparams, luv_dev, out):
 
     coef8: contiguous CUDA uint8 [3, P, 6], any spatial shape in place of P; qparams: CUDA fp64 [12]; luv_dev:
     CUDA fp64 [E, 2]; out: float32, int32 or uint8 with E·P·3 elements ([E, P, 3])."""
-    P = _rgb8_bytes(coef8)
-    _require_cuda(luv_dev, "luv")
-    if luv_dev.dtype != torch.float64 or luv_dev.dim() != 2 or luv_dev.shape[1] != 2 or luv_dev.shape[0] < 1 \
-            or not luv_dev.is_contiguous() or luv_dev.device != coef8.device:
-        raise ValueError(f"luv must be a contiguous float64 [E, 2] tensor on {coef8.device}; got {luv_dev.dtype} "
-                         f"{tuple(luv_dev.shape)} on {luv_dev.device}")
-    E = luv_dev.shape[0]
-    odt = _ENHANCED_DTYPES.get(out.dtype) if torch.is_tensor(out) else None
-    if odt is None:
-        raise ValueError("out must be a float32, int32 or uint8 tensor")
-    st = L.lib().rti_relight_rgb8(_vp(coef8), P, _rgb8_qparams_dev(qparams, coef8), _vp(luv_dev), E,
+    P = _bytes_map(coef8, 18, "three blocks of 6 bytes")
+    luv, E = _luv_arg(luv_dev, coef8)
+    odt = _out8_dtype(out)
+    st = L.lib().rti_relight_rgb8(_vp(coef8), P, _qparams_arg(qparams, torch.float64, 12, coef8), luv, E,
                                   _map_out(out, "out", out.dtype, E * P * 3, coef8), odt, _stream_of(coef8))
     L.check(st, "rti_relight_rgb8")
     return out
@@ -2110,15 +2049,8 @@ def relight_rgb8(q, lu, lv, *, out_dtype=torch.float32):
 
     q: a ``QuantisedRGB`` on the GPU.  lu, lv: scalars or E directions.  Returns [E, H, W, 3], squeezed to
     [H, W, 3] for scalar directions, in out_dtype: float32, or int32 / uint8 converted as ``relight`` does."""
-    _quantised_rgb(q)
-    if out_dtype not in _ENHANCED_DTYPES:
-        raise ValueError("out_dtype must be float32, int32 or uint8")
-    scalar = np.ndim(lu) == 0 and np.ndim(lv) == 0
-    luv = np.stack([np.asarray(lu, np.float64).ravel(), np.asarray(lv, np.float64).ravel()], -1)
-    luv_d = torch.as_tensor(np.ascontiguousarray(luv), device=q.device)
-    out = torch.empty((luv.shape[0],) + q.shape + (3,), dtype=out_dtype, device=q.device)
-    relight_rgb8_into(q.coef, q.qparams, luv_d, out)
-    return out[0] if scalar else out
+    _quantised(q, QuantisedRGB)
+    return _relight8(q, lu, lv, out_dtype, lambda luv_d, out: relight_rgb8_into(q.coef, q.qparams, luv_d, out))
 
 
 def rgb8_normals_into(coef8, qparams, normals, kind=None, peak=None, *, normal_layout="pixel", weights=None):
@@ -2127,8 +2059,9 @@ def rgb8_normals_into(coef8, qparams, normals, kind=None, peak=None, *, normal_l
     coef8 / qparams as ``relight_rgb8_into``; normals: fp32 with 3 values per pixel, [P, 3] (normal_layout="pixel")
     or [3, P]; kind: uint8 [P] or None; peak: fp32 [P] or None; weights: None (0.299, 0.587, 0.114) or three
     values (R, G, B)."""
-    P = _rgb8_bytes(coef8)
-    st = L.lib().rti_rgb8_normals(_vp(coef8), P, _rgb8_qparams_dev(qparams, coef8), _luma_weights(weights),
+    P = _bytes_map(coef8, 18, "three blocks of 6 bytes")
+    st = L.lib().rti_rgb8_normals(_vp(coef8), P, _qparams_arg(qparams, torch.float64, 12, coef8),
+                                  _luma_weights(weights),
                                   _map_out(normals, "normals", torch.float32, 3 * P, coef8),
                                   _normal_layout_id(normal_layout),
                                   None if kind is None else _map_out(kind, "kind", torch.uint8, P, coef8),
@@ -2145,7 +2078,7 @@ def rgb8_normals(q, *, normal_layout="pixel", weights=None, return_kind=False, r
 
     q: a ``QuantisedRGB`` on the GPU; weights: None (0.299, 0.587, 0.114) or three values.  Returns what
     ``normals`` returns."""
-    _quantised_rgb(q)
+    _quantised(q, QuantisedRGB)
     nl = _normal_layout_id(normal_layout)
     n, kind, peak = _normal_outputs(q.shape, nl, return_kind, return_peak, q.device)
     rgb8_normals_into(q.coef, q.qparams, n, kind, peak, normal_layout=nl, weights=weights)

@@ -6,7 +6,9 @@ exact: bytes, and bit patterns of fp32 / fp64 / int32 values.
 Sizes: a lane owns 4 pixels, a wave 256, a workgroup 1024, so 1 and 7 are a partial wave on the one-pixel path
 (P % 4 != 0), 255 is one pixel short of a wave, 256 one full wave, 1023 and 1024 the workgroup seam, 1028 a second
 workgroup whose only wave holds 4 pixels (P % 4 == 0: a full wave on the vector path and a partial one), 3077 four
-workgroups with P % 4 != 0.  Maps run in both layouts, dense and with a padded channel stride, 16-byte aligned and
+workgroups with P % 4 != 0.  The quantiser also runs BIG = 768·1024 + 1024 + 76 = 787532 pixels: the extremes' grid
+is capped at 768 workgroups of 1024 pixels, so two workgroups fold a second chunk there and the tail kernel folds
+768 partials, three per lane.  Maps run in both layouts, dense and with a padded channel stride, 16-byte aligned and
 4 bytes off; the bytes 8-byte aligned and off it; every output between guard elements."""
 import ctypes
 import functools
@@ -23,6 +25,7 @@ from rti import api
 
 pytestmark = pytest.mark.gpu
 
+BIG = 768 * 1024 + 1024 + 76
 SIZES = [1, 7, 255, 256, 1023, 1024, 1028, 3077]
 ES = [1, 3]
 OUT_DTYPES = [torch.float32, torch.int32, torch.uint8]
@@ -116,7 +119,7 @@ VARIANTS = {"dense": dict(), "padded": dict(pad=8), "padded off the vector": dic
 
 @pytest.mark.parametrize("variant", sorted(VARIANTS))
 @pytest.mark.parametrize("layout", ["pixel", "planar"])
-@pytest.mark.parametrize("P", SIZES)
+@pytest.mark.parametrize("P", SIZES + [BIG])
 def test_quantiser_is_the_hosts(cuda, P, layout, variant):
     m, want_qp, want_raw, want_deq = case(P)
     qp, c8 = run_quantiser(cuda, m, layout, **VARIANTS[variant])
