@@ -846,8 +846,8 @@ int     rti_hsh8_normals(const uint8_t* coef8, int basis, int64_t P, const float
  * 16-byte aligned with a channel stride that is a multiple of 4, coef8 8-byte aligned, out aligned as
  * rti_relight_lrgb requires (16 bytes; U8: 4) and normals / kind / peak as rti_ptm_normals requires (16 / 4 / 16);
  * anything else, and the last partial 256-pixel chunk, runs one pixel per lane with the same arithmetic and bits.
- * Not built: planar or strided coef8, diffuse gain or specular rendering from the bytes, a one-pass relight of fp32
- * RGB maps. */
+ * Not built: planar or strided coef8, a one-pass relight of fp32 RGB maps.  (Diffuse gain and specular rendering
+ * from the bytes: rti_relight_rgb8_enhanced, below.) */
 int64_t rti_rgb8_qparams_workspace(int64_t P);
 int rti_rgb8_qparams(const float* coef, int coef_layout, int64_t coef_channel_stride, int64_t P,
                      void* workspace, double* qparams, rti_stream_t stream);
@@ -858,6 +858,57 @@ int rti_relight_rgb8(const uint8_t* coef8, int64_t P, const double* qparams,
 int rti_rgb8_normals(const uint8_t* coef8, int64_t P, const double* qparams, const float* w /* HOST, NULL ok */,
                      float* normals, int normal_layout, uint8_t* kind /* NULL ok */, float* peak /* NULL ok */,
                      rti_stream_t stream);
+
+/* ---- device: diffuse gain and specular rendering of the colour forms (rti_enhance_px.h) ----------
+ * rti_relight_enhanced's two modes for an fp32 LRGB map, the 9-byte LRGB payload and the 18-byte RGB payload: one
+ * launch, one image out[p][3] (RGB interleaved like rti_relight_lrgb's) at the light direction (lu, lv).  mode, gain,
+ * kd, ks, spec_exp, lu, lv and out_dtype are rti_relight_enhanced's; lrgb and lrgb_layout rti_relight_lrgb's; coef8,
+ * rgb8 and qparams rti_relight_lrgb8's and rti_relight_rgb8's; w rti_rgb8_normals'.  The half vector H is formed once
+ * on the host and everything travels as kernel arguments.
+ * All per-pixel arithmetic is fp64 without contraction, each expression left to right as written, converted once
+ * (F32; I32 / U8 as rti_relight).  With l a LUMINANCE coefficient vector (fp64 from fp32), (u0, v0), the kind and the
+ * normal n those rti_ptm_normals states for l, and for any coefficient vector a:
+ *   G(a) = L'(lu, lv) with a' the diffuse gain transform of a about l's (u0, v0) (the formulas of
+ *          rti_relight_enhanced with a's coefficients and l's stationary point; a itself where l has no maximum).
+ *          The transform keeps the value and the gradient of a at (u0, v0) and scales its second derivatives by g
+ *          for ANY point, so every channel keeps its colour at the luminance's peak: no fringes.
+ *   D(a) = L(lu, lv) of a, the six terms summed as rti_relight's F64 path sums them
+ *   S    = max(0, n·H)^spec_exp, n·H = n_x·H_x + n_y·H_y + n_z·H_z, the power by repeated squaring
+ * A pixel whose l is not finite (kind 4) is NaN in its three channels, in both modes.
+ * rti_relight_lrgb_enhanced: l = a0..a5 of the pixel.
+ *   diffuse gain: channel c = (double)chroma_c · G(l)
+ *   specular:     channel c = kd · ((double)chroma_c · D(l)) + ks · S      (a white highlight on the coloured term)
+ *   A NaN chroma gives NaN in its channel.  With chroma = 1 every F32 channel equals rti_relight_enhanced's output
+ *   for the luminance planes bit for bit.  36 bytes in and 3·sizeof(out) out per pixel.
+ * rti_relight_lrgb8_enhanced: a_j = (float)(((double)raw_j − bias_j)·scale_j), chroma_c = (float)((double)byte_c/255.0)
+ *   as rti_relight_lrgb8 states them, then the LRGB function: the image equals rti_relight_lrgb_enhanced's of the
+ *   dequantised map bit for bit.  (A workgroup forms the 256 possible values of each plane and of the chroma once,
+ *   in exactly this arithmetic, and a pixel looks its 9 up.)  9 bytes in per pixel.
+ * rti_relight_rgb8_enhanced: a_cj as rti_relight_rgb8 states them; l_j = (wR·r_j + wG·g_j) + wB·b_j in fp32 as
+ *   rti_rgb8_normals forms it (w: three fp32 weights on the HOST, NULL = (0.299f, 0.587f, 0.114f)).
+ *   diffuse gain: channel c = G(a_c)
+ *   specular:     channel c = kd · D(a_c) + ks · S
+ *   With weights (1,0,0), (0,1,0) or (0,0,1) the channel whose weight is 1 equals rti_relight_enhanced's output for
+ *   that dequantised fp32 map bit for bit.  18 bytes in per pixel.
+ * All: device pointers except w, stream-ordered, no allocation, no synchronisation, capturable in a hipGraph.
+ * Every argument check answers before any HIP call.  RTI_ERR_BAD_ARG: a null pointer (w may be null); P < 1; a bad
+ * layout or mode; non-finite lu, lv, gain, kd, ks or weight; gain < 0; spec_exp outside [1, 255] in specular mode;
+ * qparams off 8 bytes.  RTI_ERR_UNSUPPORTED: an out_dtype other than F32 / I32 / U8.
+ * The vector path (one lane = 4 pixels) applies under the conditions of the plain relight of each form
+ * (rti_relight_lrgb, rti_relight_lrgb8, rti_relight_rgb8); anything else, and the last partial 256-pixel chunk, runs
+ * one pixel per lane with the same arithmetic and bits.
+ * Not built: E > 1 directions per launch, a multi-GPU wrapper, planar RGB output, HSH8 enhanced rendering, enhanced
+ * rendering of three fp32 RGB maps in one pass, rti_relight_lrgb8 itself in the table form. */
+int rti_relight_lrgb_enhanced(const float* lrgb, int lrgb_layout, int64_t P,
+                              int mode, double gain, double kd, double ks, int spec_exp, double lu, double lv,
+                              void* out, int out_dtype, rti_stream_t stream);
+int rti_relight_lrgb8_enhanced(const uint8_t* coef8, const uint8_t* rgb8, int64_t P, const double* qparams,
+                               int mode, double gain, double kd, double ks, int spec_exp, double lu, double lv,
+                               void* out, int out_dtype, rti_stream_t stream);
+int rti_relight_rgb8_enhanced(const uint8_t* coef8, int64_t P, const double* qparams,
+                              const float* w /* HOST, NULL ok */,
+                              int mode, double gain, double kd, double ks, int spec_exp, double lu, double lv,
+                              void* out, int out_dtype, rti_stream_t stream);
 
 #ifdef __cplusplus
 }

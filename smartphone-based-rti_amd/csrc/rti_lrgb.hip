@@ -6,6 +6,7 @@
 //
 //     rti_lrgb_from_rgb   three PTM-6 maps (rti_fit_shared with C = 3) + the design's Gram matrix -> one LRGB map
 //     rti_relight_lrgb    one LRGB map -> E interleaved RGB images
+//     rti_relight_lrgb_enhanced   one LRGB map -> one diffuse gain or specular RGB image
 //
 // The least-squares colour needs no second pass over the stack: with G = AᵀA, a = Σ_c w_c·coef_c and the fitted
 // luminance A_n·a at light n, the c that minimises Σ_n (I_c,n − c·A_n·a)² is (aᵀG·coef_c)/(aᵀG·a), because
@@ -32,7 +33,9 @@
 
 #include "rti_basis.h"
 #include "rti_convert.h"
+#include "rti_enhance_px.h"
 #include "rti_lrgb_px.h"
+#include "rti_quant8.h"
 #include "rti_stack.h"
 
 namespace rti {
@@ -186,6 +189,44 @@ relight_lrgb_k(const float* __restrict__ lrgb, int64_t P, int vec, const double*
   }
 }
 
+// rti_relight_lrgb's kernel with one direction and the enhanced luminance in place of the plain one
+// (enhance_px::lrgb_enhanced)
+template <int CL, typename TO, int MODE>
+__global__ void __launch_bounds__(256)
+relight_lrgb_enhanced_k(const float* __restrict__ lrgb, int64_t P, int vec, enhance_px::Enhance q,
+                        TO* __restrict__ out) {
+  constexpr bool STAGE_OUT = sizeof(TO) == 4;  // fp32 / int32: 48 B per lane through the slab
+  constexpr int SLAB = slab_v4(CL == RTI_COEF_PIXEL_MAJOR ? NL : 0, STAGE_OUT ? 3 : 0);
+  __shared__ floatx4 slabs[4 * SLAB];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
+  if (wave_px >= P) return;
+  floatx4* slab = slabs + wave * SLAB;
+  if (vec && wave_px + 256 <= P) {  // wave-uniform
+    float m[4][NL];
+    load_wave<NL, CL>(lrgb, P, wave_px, lane, slab, m);
+    TO o[4][3];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) enhance_px::lrgb_enhanced<MODE, TO>(m[v], q, o[v]);
+    TO* rows = out + wave_px * 3;
+    if constexpr (STAGE_OUT)
+      store_rows_staged<3, TO>(rows, lane, slab, o);
+    else
+      quant8::store_dwords<12>(rows + 12 * lane, &o[0][0]);
+    return;
+  }
+  for (int j = 0; j < 4; ++j) {
+    const int64_t p = wave_px + 64 * j + lane;
+    if (p >= P) break;
+    float m[NL];
+    load_pixel<NL, CL>(lrgb, P, p, m);
+    TO o[3];
+    enhance_px::lrgb_enhanced<MODE, TO>(m, q, o);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[p * 3 + c] = o[c];
+  }
+}
+
 // ---- launchers ----------------------------------------------------------------------------------------------------
 
 struct CompressArgs {
@@ -234,6 +275,15 @@ void launch_relight_out(const RelightArgs& a, int odt) {
     case RTI_I32: launch_relight_t<CL, int32_t>(a); break;
     default: launch_relight_t<CL, uint8_t>(a); break;
   }
+}
+
+template <int CL>
+void launch_enhanced_t(const RelightArgs& a, const enhance_px::Enhance& q, int mode, int odt) {
+  enhance_px::with_mode_out(mode, odt, [&](auto m, auto t) {
+    using TO = decltype(t);
+    hipLaunchKernelGGL((relight_lrgb_enhanced_k<CL, TO, decltype(m)::value>), dim3(grid_1d(a.P, 1024)), dim3(256), 0,
+                       a.s, a.lrgb, a.P, a.vec, q, static_cast<TO*>(a.out));
+  });
 }
 
 }  // namespace
@@ -289,5 +339,27 @@ extern "C" int rti_relight_lrgb(const float* lrgb, int lrgb_layout, int64_t P, c
     launch_relight_out<RTI_COEF_PLANAR>(a, out_dtype);
   else
     launch_relight_out<RTI_COEF_PIXEL_MAJOR>(a, out_dtype);
+  return check_launch(E);
+}
+
+extern "C" int rti_relight_lrgb_enhanced(const float* lrgb, int lrgb_layout, int64_t P, int mode, double gain,
+                                         double kd, double ks, int spec_exp, double lu, double lv, void* out,
+                                         int out_dtype, rti_stream_t stream) {
+  const char* const E = "rti_relight_lrgb_enhanced";
+  if (int st = check_pointers(E, {lrgb, out})) return st;
+  if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", E);
+  if (lrgb_layout != RTI_COEF_PIXEL_MAJOR && lrgb_layout != RTI_COEF_PLANAR)
+    return fail(RTI_ERR_BAD_ARG, "%s: lrgb layout %d", E, lrgb_layout);
+  if (int st = enhance_px::check_enhance(E, mode, gain, kd, ks, spec_exp, lu, lv)) return st;
+  if (int st = enhance_px::check_enhance_out(E, out_dtype)) return st;
+  const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // a lane's dword / the wave's 16-byte pieces
+  const bool vec = P % 4 == 0 && aligned_to(lrgb, 16) && aligned_to(out, ovec);
+  const RelightArgs a{lrgb, P, vec ? 1 : 0, nullptr, 1, out, (hipStream_t)stream};
+  const enhance_px::Enhance q = enhance_px::enhance_args(gain, kd, ks, spec_exp, lu, lv);
+  note_launches(1);
+  if (lrgb_layout == RTI_COEF_PLANAR)
+    launch_enhanced_t<RTI_COEF_PLANAR>(a, q, mode, out_dtype);
+  else
+    launch_enhanced_t<RTI_COEF_PIXEL_MAJOR>(a, q, mode, out_dtype);
   return check_launch(E);
 }

@@ -3,6 +3,7 @@
 //     rti_lrgb_qparams    one pass over an fp32 LRGB map -> the file's six scales, six biases and the chroma scale s
 //     rti_lrgb_quantise   the map + those 13 doubles -> 6 coefficient bytes and 3 colour bytes per pixel
 //     rti_relight_lrgb8   the 9 bytes + scales and biases -> E interleaved RGB images
+//     rti_relight_lrgb8_enhanced   the 9 bytes -> one diffuse gain or specular RGB image
 //
 // The arithmetic is rti/io.py's (write_ptm, _ptm_quantise, read_ptm), in fp64 from the fp32 map with FP contraction
 // off, so the bytes equal the host's and an image rendered from the bytes equals rti_relight_lrgb's of the fp32 map
@@ -24,6 +25,7 @@
 
 #include "rti_basis.h"
 #include "rti_convert.h"
+#include "rti_enhance_px.h"
 #include "rti_lrgb_px.h"
 #include "rti_quant8.h"
 #include "rti_stack.h"
@@ -233,6 +235,92 @@ void launch_relight8(const uint8_t* coef8, const uint8_t* rgb8, int64_t P, int v
                      luv, E, static_cast<TO*>(out));
 }
 
+// ---- enhanced rendering from the bytes ---------------------------------------------------------
+// A byte can only become one of 256 fp32 values, so the workgroup fills seven 256-entry tables in LDS (7 KiB; lane t
+// forms entry t of each in fp64 and rounds it once: rti_rgb8.hip's fill_tables plus the chroma's byte / 255) and a
+// pixel costs 9 LDS reads instead of six fp64 products and three fp64 divisions.  The tables hold the very values
+// dequantise_px gives, so the image is rti_relight_lrgb_enhanced's of the dequantised map bit for bit.
+
+constexpr int TAB = 256;
+
+__device__ __forceinline__ void fill_tables(const double* __restrict__ qparams, float* __restrict__ tab) {
+#pragma clang fp contract(off)
+  const double t = (double)threadIdx.x;
+#pragma unroll
+  for (int j = 0; j < K; ++j) tab[j * TAB + threadIdx.x] = (float)((t - qparams[K + j]) * qparams[j]);
+  tab[K * TAB + threadIdx.x] = (float)(t / 255.0);
+}
+
+__device__ __forceinline__ void lookup_px(const uint8_t (&cb)[K], const uint8_t (&rb)[3], const float* __restrict__ tab,
+                                          float (&m)[NL]) {
+#pragma unroll
+  for (int j = 0; j < K; ++j) m[j] = tab[j * TAB + cb[j]];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) m[K + c] = tab[K * TAB + rb[c]];
+}
+
+template <typename TO, int MODE>
+__global__ void __launch_bounds__(256)
+relight_lrgb8_enhanced_k(const uint8_t* __restrict__ coef8, const uint8_t* __restrict__ rgb8, int64_t P, int vec,
+                         const double* __restrict__ qparams, enhance_px::Enhance q, TO* __restrict__ out) {
+  constexpr bool STAGE_OUT = sizeof(TO) == 4;  // fp32 / int32: 48 B per lane through the slab
+  constexpr int SLAB = slab_v4(0, STAGE_OUT ? 3 : 0);
+  __shared__ floatx4 slabs[4 * SLAB];
+  __shared__ float tab[(K + 1) * TAB];
+  fill_tables(qparams, tab);
+  __syncthreads();  // the one workgroup barrier: waves may leave below
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
+  if (wave_px >= P) return;
+  floatx4* slab = slabs + wave * SLAB;
+  if (vec && wave_px + 256 <= P) {  // wave-uniform
+    const int64_t p0 = wave_px + 4 * lane;
+    union {
+      u32x2 v[3];
+      uint8_t b[4][K];
+    } cb;
+    union {
+      uint32_t v[3];
+      uint8_t b[4][3];
+    } rb;
+    const u32x2* c2 = reinterpret_cast<const u32x2*>(coef8 + p0 * K);
+    const uint32_t* r4 = reinterpret_cast<const uint32_t*>(rgb8 + p0 * 3);
+#pragma unroll
+    for (int w = 0; w < 3; ++w) {
+      cb.v[w] = c2[w];
+      rb.v[w] = r4[w];
+    }
+    TO o[4][3];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      float m[NL];
+      lookup_px(cb.b[v], rb.b[v], tab, m);
+      enhance_px::lrgb_enhanced<MODE, TO>(m, q, o[v]);
+    }
+    TO* rows = out + wave_px * 3;
+    if constexpr (STAGE_OUT)
+      store_rows_staged<3, TO>(rows, lane, slab, o);
+    else
+      store_dwords<12>(rows + 12 * lane, &o[0][0]);
+    return;
+  }
+  for (int j = 0; j < 4; ++j) {
+    const int64_t p = wave_px + 64 * j + lane;
+    if (p >= P) break;
+    uint8_t cb[K], rb[3];
+#pragma unroll
+    for (int i = 0; i < K; ++i) cb[i] = coef8[p * K + i];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) rb[c] = rgb8[p * 3 + c];
+    float m[NL];
+    lookup_px(cb, rb, tab, m);
+    TO o[3];
+    enhance_px::lrgb_enhanced<MODE, TO>(m, q, o);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) out[p * 3 + c] = o[c];
+  }
+}
+
 int check_lrgb_layout(const char* entry, int layout) {
   if (layout != RTI_COEF_PIXEL_MAJOR && layout != RTI_COEF_PLANAR)
     return fail(RTI_ERR_BAD_ARG, "%s: lrgb layout %d", entry, layout);
@@ -305,5 +393,26 @@ extern "C" int rti_relight_lrgb8(const uint8_t* coef8, const uint8_t* rgb8, int6
     case RTI_I32: launch_relight8<int32_t>(coef8, rgb8, P, vec, qparams, luv, E_, out, (hipStream_t)stream); break;
     default: launch_relight8<uint8_t>(coef8, rgb8, P, vec, qparams, luv, E_, out, (hipStream_t)stream); break;
   }
+  return check_launch(E);
+}
+
+extern "C" int rti_relight_lrgb8_enhanced(const uint8_t* coef8, const uint8_t* rgb8, int64_t P, const double* qparams,
+                                          int mode, double gain, double kd, double ks, int spec_exp, double lu,
+                                          double lv, void* out, int out_dtype, rti_stream_t stream) {
+  const char* const E = "rti_relight_lrgb8_enhanced";
+  if (int st = check_pointers(E, {coef8, rgb8, qparams, out})) return st;
+  if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", E);
+  if (int st = enhance_px::check_enhance(E, mode, gain, kd, ks, spec_exp, lu, lv)) return st;
+  if (int st = enhance_px::check_enhance_out(E, out_dtype)) return st;
+  if (!aligned_to(qparams, 8)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 8-byte aligned", E);
+  const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // a lane's dword / the wave's 16-byte pieces
+  const int vec = P % 4 == 0 && aligned_to(coef8, 8) && aligned_to(rgb8, 4) && aligned_to(out, ovec) ? 1 : 0;
+  const enhance_px::Enhance q = enhance_px::enhance_args(gain, kd, ks, spec_exp, lu, lv);
+  note_launches(1);
+  enhance_px::with_mode_out(mode, out_dtype, [&](auto m, auto t) {
+    using TO = decltype(t);
+    hipLaunchKernelGGL((relight_lrgb8_enhanced_k<TO, decltype(m)::value>), dim3(grid_1d(P, 1024)), dim3(256), 0,
+                       (hipStream_t)stream, coef8, rgb8, P, vec, qparams, q, static_cast<TO*>(out));
+  });
   return check_launch(E);
 }

@@ -33,14 +33,15 @@
 #include <type_traits>
 
 #include "rti_convert.h"
+#include "rti_enhance_px.h"
 #include "rti_ptm_px.h"
-#include "rti_shade.h"
 #include "rti_stack.h"
 
 namespace rti {
 namespace {
 
-using namespace ptm_px;  // K = 6 and rti_ptm_normals' per-pixel function, shared with rti_rgb8.hip
+using namespace ptm_px;      // K = 6 and rti_ptm_normals' per-pixel function, shared with rti_rgb8.hip
+using namespace enhance_px;  // rti_relight_enhanced's, shared with the colour forms
 typedef double doublex2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ void wave_lds_sync() {
@@ -49,46 +50,8 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-// ---- per-pixel arithmetic (fp64, no contraction; ptm_value, ptm_peak and ptm_normal: rti_ptm_px.h) ------------
-
-// diffuse gain g: the curvature scaled by g about the unprojected stationary point, whose location and height
-// stay; pixels without a maximum keep their coefficients
-__device__ __forceinline__ double diffuse_gain_value(const double (&a)[K], const Peak& k, double g, double lu, double lv) {
-#pragma clang fp contract(off)
-  const double h = 1.0 - g, u0 = k.u0, v0 = k.v0;
-  double b[K];
-  b[0] = g * a[0];
-  b[1] = g * a[1];
-  b[2] = g * a[2];
-  b[3] = h * (2.0 * a[0] * u0 + a[2] * v0) + a[3];
-  b[4] = h * (2.0 * a[1] * v0 + a[2] * u0) + a[4];
-  b[5] = h * (a[0] * (u0 * u0) + a[1] * (v0 * v0) + a[2] * u0 * v0) + (a[3] - b[3]) * u0 + (a[4] - b[4]) * v0 + a[5];
-#pragma unroll
-  for (int i = 0; i < K; ++i) b[i] = k.has_max ? b[i] : a[i];
-  return k.finite ? ptm_value(b, lu, lv) : (double)NAN;
-}
-
-struct Enhance {
-  double gain, kd, ks;
-  int e;
-  double lu, lv;
-  double hx, hy, hz;  // the half vector between the light and the viewer (0, 0, 1), unit length
-};
-
-template <int MODE>
-__device__ __forceinline__ double enhanced_value(const double (&a)[K], const Enhance& q) {
-#pragma clang fp contract(off)
-  const Peak k = ptm_peak(a);
-  if constexpr (MODE == RTI_ENHANCE_DIFFUSE_GAIN) {
-    return diffuse_gain_value(a, k, q.gain, q.lu, q.lv);
-  } else {
-    double n[3];
-    ptm_normal(a, k, n);
-    const double c = n[0] * q.hx + n[1] * q.hy + n[2] * q.hz;
-    const double v = q.kd * ptm_value(a, q.lu, q.lv) + q.ks * powi(c > 0.0 ? c : 0.0, q.e);
-    return k.finite ? v : (double)NAN;
-  }
-}
+// ---- per-pixel arithmetic: ptm_value, ptm_peak and ptm_normal in rti_ptm_px.h; diffuse_gain_value, Enhance and
+// enhanced_value in rti_enhance_px.h, shared with the colour forms
 
 // ---- coefficient loads ------------------------------------------------------------------------------------------
 
@@ -364,20 +327,12 @@ extern "C" int rti_relight_enhanced(const void* coef, int coef_dtype, int basis,
   const char* const E = "rti_relight_enhanced";
   if (int st = check_pointers(E, {coef, out})) return st;
   if (int st = check_ptm_map(E, P, coef_layout)) return st;
-  if (mode != RTI_ENHANCE_DIFFUSE_GAIN && mode != RTI_ENHANCE_SPECULAR) return fail(RTI_ERR_BAD_ARG, "%s: mode %d", E, mode);
-  if (!std::isfinite(lu) || !std::isfinite(lv)) return fail(RTI_ERR_BAD_ARG, "%s: non-finite light direction", E);
-  if (!std::isfinite(gain) || !std::isfinite(kd) || !std::isfinite(ks))
-    return fail(RTI_ERR_BAD_ARG, "%s: non-finite gain, kd or ks", E);
-  if (gain < 0.0) return fail(RTI_ERR_BAD_ARG, "%s: gain %g < 0", E, gain);
-  if (mode == RTI_ENHANCE_SPECULAR && (spec_exp < 1 || spec_exp > 255))
-    return fail(RTI_ERR_BAD_ARG, "%s: spec_exp %d outside [1, 255]", E, spec_exp);
+  if (int st = check_enhance(E, mode, gain, kd, ks, spec_exp, lu, lv)) return st;
   if (int st = check_ptm_types(E, basis, coef_dtype)) return st;
-  if (out_dtype != RTI_F32 && out_dtype != RTI_I32 && out_dtype != RTI_U8)
-    return fail(RTI_ERR_UNSUPPORTED, "%s: out dtype %d", E, out_dtype);
-  const LightFrame f = light_frame(lu, lv);
+  if (int st = check_enhance_out(E, out_dtype)) return st;
   const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // bytes of a lane's 4 outputs
   const bool vec = P % 4 == 0 && aligned_to(coef, 16) && aligned_to(out, ovec);
-  const EnhanceArgs a{coef, P, vec ? 1 : 0, Enhance{gain, kd, ks, spec_exp, lu, lv, f.hx, f.hy, f.hz}, out,
+  const EnhanceArgs a{coef, P, vec ? 1 : 0, enhance_args(gain, kd, ks, spec_exp, lu, lv), out,
                       (hipStream_t)stream};
   if (coef_dtype == RTI_F64)
     launch_enhanced_cl<double>(a, coef_layout, mode, out_dtype);

@@ -4,6 +4,7 @@
 //     rti_rgb8_quantise   the maps + those 12 doubles -> three blocks of 6 bytes per pixel, R then G then B
 //     rti_relight_rgb8    the 18 bytes + scales and biases -> E interleaved RGB images
 //     rti_rgb8_normals    the 18 bytes -> rti_ptm_normals of their fp32 luminance map
+//     rti_relight_rgb8_enhanced   the 18 bytes -> one diffuse gain or specular RGB image
 //
 // The quantiser's arithmetic is rti/io.py's (write_ptm(format="rgb"), _ptm_quantise), in fp64 from the fp32 maps with
 // FP contraction off, so the bytes equal the host's.  A dequantised coefficient is the fp32 value read_ptm builds,
@@ -32,6 +33,7 @@
 
 #include "rti_basis.h"
 #include "rti_convert.h"
+#include "rti_enhance_px.h"
 #include "rti_hsh_px.h"
 #include "rti_lrgb_px.h"
 #include "rti_ptm_px.h"
@@ -347,6 +349,57 @@ rgb8_normals_k(const uint8_t* __restrict__ coef8, int64_t P, int vec, const doub
   }
 }
 
+// rti_relight_rgb8's loads and tables, rti_rgb8_normals' luminance, and every channel enhanced under the
+// luminance's peak (enhance_px::rgb_enhanced)
+template <typename TO, int MODE>
+__global__ void __launch_bounds__(256)
+relight_rgb8_enhanced_k(const uint8_t* __restrict__ coef8, int64_t P, int vec, const double* __restrict__ qparams,
+                        Weights w, enhance_px::Enhance q, TO* __restrict__ out) {
+  constexpr bool STAGE_OUT = sizeof(TO) == 4;  // fp32 / int32: 48 B per lane through the slab
+  constexpr int SLAB = slab_v4(0, STAGE_OUT ? 3 : 0);
+  __shared__ floatx4 slabs[4 * SLAB];
+  __shared__ float tab[K * TAB];
+  fill_tables(qparams, tab);
+  __syncthreads();  // the one workgroup barrier: waves may leave below
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
+  if (wave_px >= P) return;
+  floatx4* slab = slabs + wave * SLAB;
+  if (vec && wave_px + 256 <= P) {  // wave-uniform
+    Bytes4 r;
+    load_bytes4(coef8, P, wave_px + 4 * lane, r);
+    TO o[4][3];
+#pragma unroll
+    for (int v = 0; v < 4; ++v) {
+      float c[3][K], l[K];
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) dequantise_px(r.c[ch].b[v], tab, c[ch]);
+      luminance(c, w.r, w.g, w.b, l);
+      enhance_px::rgb_enhanced<MODE, TO>(c, l, q, o[v]);
+    }
+    TO* rows = out + wave_px * 3;
+    if constexpr (STAGE_OUT)
+      store_rows_staged<3, TO>(rows, lane, slab, o);
+    else
+      store_dwords<12>(rows + 12 * lane, &o[0][0]);
+    return;
+  }
+  for (int j = 0; j < 4; ++j) {
+    const int64_t p = wave_px + 64 * j + lane;
+    if (p >= P) break;
+    uint8_t cb[3][K];
+    load_bytes1(coef8, P, p, cb);
+    float c[3][K], l[K];
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) dequantise_px(cb[ch], tab, c[ch]);
+    luminance(c, w.r, w.g, w.b, l);
+    TO o[3];
+    enhance_px::rgb_enhanced<MODE, TO>(c, l, q, o);
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) out[p * 3 + ch] = o[ch];
+  }
+}
+
 // ---- launchers and checks -----------------------------------------------------------------------------------------
 
 template <typename TO>
@@ -459,5 +512,29 @@ extern "C" int rti_rgb8_normals(const uint8_t* coef8, int64_t P, const double* q
   else
     hipLaunchKernelGGL((rgb8_normals_k<RTI_NORMAL_PIXEL_MAJOR>), dim3(grid_1d(P, 1024)), dim3(256), 0,
                        (hipStream_t)stream, coef8, P, vec, qparams, wt, normals, kind, peak);
+  return check_launch(E);
+}
+
+extern "C" int rti_relight_rgb8_enhanced(const uint8_t* coef8, int64_t P, const double* qparams, const float* w,
+                                         int mode, double gain, double kd, double ks, int spec_exp, double lu,
+                                         double lv, void* out, int out_dtype, rti_stream_t stream) {
+  const char* const E = "rti_relight_rgb8_enhanced";
+  if (int st = check_pointers(E, {coef8, qparams, out})) return st;
+  if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", E);
+  if (int st = enhance_px::check_enhance(E, mode, gain, kd, ks, spec_exp, lu, lv)) return st;
+  const Weights wt{w ? w[0] : 0.299f, w ? w[1] : 0.587f, w ? w[2] : 0.114f};
+  if (!std::isfinite(wt.r) || !std::isfinite(wt.g) || !std::isfinite(wt.b))
+    return fail(RTI_ERR_BAD_ARG, "%s: non-finite weight", E);
+  if (int st = enhance_px::check_enhance_out(E, out_dtype)) return st;
+  if (!aligned_to(qparams, 8)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 8-byte aligned", E);
+  const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // a lane's dword / the wave's 16-byte pieces
+  const int vec = P % 4 == 0 && aligned_to(coef8, 8) && aligned_to(out, ovec) ? 1 : 0;
+  const enhance_px::Enhance q = enhance_px::enhance_args(gain, kd, ks, spec_exp, lu, lv);
+  note_launches(1);
+  enhance_px::with_mode_out(mode, out_dtype, [&](auto m, auto t) {
+    using TO = decltype(t);
+    hipLaunchKernelGGL((relight_rgb8_enhanced_k<TO, decltype(m)::value>), dim3(grid_1d(P, 1024)), dim3(256), 0,
+                       (hipStream_t)stream, coef8, P, vec, qparams, wt, q, static_cast<TO*>(out));
+  });
   return check_launch(E);
 }

@@ -36,6 +36,9 @@ bara96/Smartphone-based-RTI: analysis.py:196-411, interactive_relighting.py:11-3
     n = rti.rgb8_normals(p)                          # normals of the luminance, from the bytes
     rti.write_ptm("object.ptm", p)                   # and back: rti.read_ptm8("object.ptm")[1].to("cuda")
 
+    rgb = rti.relight_rgb8_enhanced(p, 0.3, -0.2, "specular", kd=0.4, ks=150, exp=75, out_dtype=torch.uint8)
+    rgb = rti.relight_lrgb8_enhanced(q, 0.3, -0.2, "diffuse_gain", gain=3.5)      # and relight_lrgb_enhanced(m, ...)
+
 Compute runs in HIP kernels of librti.so (include/rti.h); importing this
 package does not touch the GPU.
 """
@@ -54,7 +57,9 @@ from .api import (BASES, FitAccumulator, apply_operator, basis_eval, basis_id, b
                   quantise_hsh, relight_hsh8, relight_hsh8_into,
                   hsh8_normals, hsh8_normals_into, hsh_normals, hsh_normals_into, peak_grid_points, peak_table,
                   QuantisedRGB, dequantise_rgb, quantise_rgb, relight_rgb8, relight_rgb8_into, rgb8_normals,
-                  rgb8_normals_into, rgb8_qparams_into, rgb8_qparams_workspace, rgb8_quantise_into)
+                  rgb8_normals_into, rgb8_qparams_into, rgb8_qparams_workspace, rgb8_quantise_into,
+                  relight_lrgb_enhanced, relight_lrgb_enhanced_into, relight_lrgb8_enhanced,
+                  relight_lrgb8_enhanced_into, relight_rgb8_enhanced, relight_rgb8_enhanced_into)
 from .io import read_ptm, read_ptm8, read_rti, write_ptm, write_rti
 
 __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_into", "fit_chunked",
@@ -72,7 +77,9 @@ __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_in
            "hsh_quantise_into", "quantise_hsh", "relight_hsh8", "relight_hsh8_into", "hsh8_normals",
            "hsh8_normals_into", "hsh_normals", "hsh_normals_into", "peak_grid_points", "peak_table", "QuantisedRGB",
            "dequantise_rgb", "quantise_rgb", "relight_rgb8", "relight_rgb8_into", "rgb8_normals", "rgb8_normals_into",
-           "rgb8_qparams_into", "rgb8_qparams_workspace", "rgb8_quantise_into", "read_ptm", "read_ptm8", "write_ptm",
+           "rgb8_qparams_into", "rgb8_qparams_workspace", "rgb8_quantise_into", "relight_lrgb_enhanced",
+           "relight_lrgb_enhanced_into", "relight_lrgb8_enhanced", "relight_lrgb8_enhanced_into",
+           "relight_rgb8_enhanced", "relight_rgb8_enhanced_into", "read_ptm", "read_ptm8", "write_ptm",
            "read_rti", "write_rti", "library_path", "load"]
 
 __version__ = "0.1.0"

@@ -186,6 +186,12 @@ SIGNATURES = {
     "rti_relight_rgb8": (_c_int, [_c_void_p, _c_i64, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_int, _c_void_p]),
     "rti_rgb8_normals": (_c_int, [_c_void_p, _c_i64, _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p,
                                   _c_void_p]),
+    "rti_relight_lrgb_enhanced": (_c_int, [_c_void_p, _c_int, _c_i64, _c_int, _c_double, _c_double, _c_double, _c_int,
+                                           _c_double, _c_double, _c_void_p, _c_int, _c_void_p]),
+    "rti_relight_lrgb8_enhanced": (_c_int, [_c_void_p, _c_void_p, _c_i64, _c_void_p, _c_int, _c_double, _c_double,
+                                            _c_double, _c_int, _c_double, _c_double, _c_void_p, _c_int, _c_void_p]),
+    "rti_relight_rgb8_enhanced": (_c_int, [_c_void_p, _c_i64, _c_void_p, _c_void_p, _c_int, _c_double, _c_double,
+                                           _c_double, _c_int, _c_double, _c_double, _c_void_p, _c_int, _c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -2085,6 +2085,105 @@ def rgb8_normals(q, *, normal_layout="pixel", weights=None, return_kind=False, r
     return _normal_results(n, kind, peak, q.shape, nl)
 
 
+# ---- diffuse gain and specular rendering of the colour forms ----------------
+
+def _enhance_scalars(mode, gain, kd, ks, exp, lu, lv):
+    """What the three ``rti_relight_*_enhanced`` entries take between their map and their output."""
+    return (_enhance_mode_id(mode), float(gain), float(kd), float(ks), int(exp), float(lu), float(lv))
+
+
+def relight_lrgb_enhanced_into(lrgb, lu, lv, mode, out, *, gain=1.0, kd=1.0, ks=0.0, exp=1, layout="pixel"):
+    """Launch ``rti_relight_lrgb_enhanced`` on preallocated tensors (no allocation, graph-capturable).
+
+    lrgb as ``relight_lrgb_into``; mode, gain, kd, ks, exp as ``relight_enhanced_into``; out: float32, int32 or
+    uint8 with P·3 elements ([P, 3], RGB interleaved)."""
+    P = _lrgb_map(lrgb)
+    odt = _out8_dtype(out)
+    st = L.lib().rti_relight_lrgb_enhanced(_vp(lrgb), _layout_id(layout), P,
+                                           *_enhance_scalars(mode, gain, kd, ks, exp, lu, lv),
+                                           _map_out(out, "out", out.dtype, P * 3, lrgb), odt, _stream_of(lrgb))
+    L.check(st, "rti_relight_lrgb_enhanced")
+    return out
+
+
+def relight_lrgb8_enhanced_into(coef8, rgb8, qparams, lu, lv, mode, out, *, gain=1.0, kd=1.0, ks=0.0, exp=1):
+    """Launch ``rti_relight_lrgb8_enhanced`` on preallocated tensors (no allocation, graph-capturable).
+
+    coef8 / rgb8 / qparams as ``relight_lrgb8_into``; the rest as ``relight_lrgb_enhanced_into``."""
+    P = _bytes_map(coef8, 6, "6 bytes")
+    _require_cuda(rgb8, "rgb8")
+    if rgb8.dtype != torch.uint8 or not rgb8.is_contiguous() or rgb8.numel() != 3 * P or rgb8.device != coef8.device:
+        raise ValueError(f"rgb8 must be a contiguous uint8 tensor of {3 * P} elements on {coef8.device}; got "
+                         f"{rgb8.dtype} {tuple(rgb8.shape)} on {rgb8.device}")
+    odt = _out8_dtype(out)
+    st = L.lib().rti_relight_lrgb8_enhanced(_vp(coef8), _vp(rgb8), P, _qparams_arg(qparams, torch.float64, 13, coef8),
+                                            *_enhance_scalars(mode, gain, kd, ks, exp, lu, lv),
+                                            _map_out(out, "out", out.dtype, P * 3, coef8), odt, _stream_of(coef8))
+    L.check(st, "rti_relight_lrgb8_enhanced")
+    return out
+
+
+def relight_rgb8_enhanced_into(coef8, qparams, lu, lv, mode, out, *, gain=1.0, kd=1.0, ks=0.0, exp=1, weights=None):
+    """Launch ``rti_relight_rgb8_enhanced`` on preallocated tensors (no allocation, graph-capturable).
+
+    coef8 / qparams as ``relight_rgb8_into``; weights as ``rgb8_normals_into``; the rest as
+    ``relight_lrgb_enhanced_into``."""
+    P = _bytes_map(coef8, 18, "three blocks of 6 bytes")
+    odt = _out8_dtype(out)
+    st = L.lib().rti_relight_rgb8_enhanced(_vp(coef8), P, _qparams_arg(qparams, torch.float64, 12, coef8),
+                                           _luma_weights(weights),
+                                           *_enhance_scalars(mode, gain, kd, ks, exp, lu, lv),
+                                           _map_out(out, "out", out.dtype, P * 3, coef8), odt, _stream_of(coef8))
+    L.check(st, "rti_relight_rgb8_enhanced")
+    return out
+
+
+def _enhanced_rgb_out(spatial, out_dtype, device):
+    if out_dtype not in _ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    return torch.empty(tuple(spatial) + (3,), dtype=out_dtype, device=device)
+
+
+def relight_lrgb_enhanced(lrgb, lu, lv, mode, *, gain=1.0, kd=1.0, ks=0.0, exp=1, layout="pixel",
+                          out_dtype=torch.float32):
+    """One enhanced RGB rendering of an LRGB map at the light direction (lu, lv) on the GPU in one launch
+    (``rti_relight_lrgb_enhanced``): ``relight_enhanced`` of the luminance under the pixel's chroma.
+
+    mode="diffuse_gain": chroma_c · L'(lu, lv), the luminance's curvature scaled by ``gain`` about its peak.
+    mode="specular": kd·chroma_c·L(lu, lv) + ks·max(0, n·H)^exp, a white highlight at the luminance's normal.
+    lrgb as ``relight_lrgb``.  Returns [H, W, 3] in out_dtype: float32, or int32 / uint8 converted as ``relight``
+    does.  With chroma 1 every channel is ``relight_enhanced`` of the luminance planes bit for bit."""
+    _require_cuda(lrgb, "lrgb")
+    cl = _layout_id(layout)
+    out = _enhanced_rgb_out(_coef_spatial(lrgb, 9, cl), out_dtype, lrgb.device)
+    return relight_lrgb_enhanced_into(lrgb.contiguous(), lu, lv, mode, out, gain=gain, kd=kd, ks=ks, exp=exp, layout=cl)
+
+
+def relight_lrgb8_enhanced(q, lu, lv, mode, *, gain=1.0, kd=1.0, ks=0.0, exp=1, out_dtype=torch.float32):
+    """``relight_lrgb_enhanced`` of a quantised LRGB map, from its 9 bytes per pixel in one launch
+    (``rti_relight_lrgb8_enhanced``): ``relight_lrgb_enhanced(dequantise_lrgb(q), ...)`` bit for bit.
+
+    q: a ``QuantisedLRGB`` on the GPU.  Returns [H, W, 3] in out_dtype."""
+    _quantised(q, QuantisedLRGB)
+    out = _enhanced_rgb_out(q.shape, out_dtype, q.device)
+    return relight_lrgb8_enhanced_into(q.coef, q.rgb, q.qparams, lu, lv, mode, out, gain=gain, kd=kd, ks=ks, exp=exp)
+
+
+def relight_rgb8_enhanced(q, lu, lv, mode, *, gain=1.0, kd=1.0, ks=0.0, exp=1, out_dtype=torch.float32, weights=None):
+    """One enhanced RGB rendering of a quantised RGB PTM at (lu, lv), from its 18 bytes per pixel in one launch
+    (``rti_relight_rgb8_enhanced``).  The peak and the normal are those of the luminance ``rgb8_normals`` reads
+    (weights: None = 0.299, 0.587, 0.114, or three values); every channel keeps its own coefficients.
+
+    mode="diffuse_gain": each channel's curvature scaled by ``gain`` about the luminance's peak, so the colour at
+    the peak stays and the channels do not part.  mode="specular": kd·L_c(lu, lv) + ks·max(0, n·H)^exp.
+    q: a ``QuantisedRGB`` on the GPU.  Returns [H, W, 3] in out_dtype.  With a unit weight on channel c, that
+    channel is ``relight_enhanced(dequantise_rgb(q)[c], ...)`` bit for bit."""
+    _quantised(q, QuantisedRGB)
+    out = _enhanced_rgb_out(q.shape, out_dtype, q.device)
+    return relight_rgb8_enhanced_into(q.coef, q.qparams, lu, lv, mode, out, gain=gain, kd=kd, ks=ks, exp=exp,
+                                      weights=weights)
+
+
 # ---- light operators (RBF, fused PTM/HSH fit + evaluation) ----------------------------------
 
 def _query(qu, qv):

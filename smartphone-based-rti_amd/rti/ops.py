@@ -2,7 +2,8 @@
 ``fit_robust`` / ``fit_accumulate`` / ``fit_accum_solve`` / ``fit_residual`` / ``relight`` / ``ptm_normals`` /
 ``relight_enhanced`` / ``map_unsharp`` / ``shade_normals`` / ``lrgb_from_rgb`` / ``relight_lrgb`` /
 ``lrgb_quantise`` / ``relight_lrgb8`` / ``hsh_quantise`` / ``relight_hsh8`` / ``hsh_normals`` / ``hsh8_normals`` /
-``rgb8_quantise`` / ``relight_rgb8`` / ``rgb8_normals``.
+``rgb8_quantise`` / ``relight_rgb8`` / ``rgb8_normals`` / ``relight_lrgb_enhanced`` / ``relight_lrgb8_enhanced`` /
+``relight_rgb8_enhanced``.
 
 They let the fit and relight kernels sit inside torch programs (and
 ``torch.library`` fake-tensor tracing) while the compute stays in librti's
@@ -593,3 +594,69 @@ def rgb8_normals(coef8: torch.Tensor, qparams: torch.Tensor, normals_planar: boo
 @rgb8_normals.register_fake
 def _(coef8, qparams, normals_planar=False, weights=None):
     return _normal_triple(coef8, coef8.shape[1], normals_planar)
+
+
+# ---- diffuse gain and specular rendering of the colour forms ----------------
+
+def _enhanced_rgb_out(like, P, out_dtype):
+    if out_dtype not in api._ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    return like.new_empty((P, 3), dtype=out_dtype)
+
+
+@torch.library.custom_op("rti::relight_lrgb_enhanced", mutates_args=())
+def relight_lrgb_enhanced(lrgb: torch.Tensor, lu: float, lv: float, mode: int, gain: float = 1.0, kd: float = 1.0,
+                          ks: float = 0.0, exp: int = 1, planar: bool = False,
+                          out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """One enhanced RGB rendering of an LRGB map at (lu, lv) (``rti_relight_lrgb_enhanced``).  lrgb CUDA fp32
+    [P, 9] (or [9, P] if planar), mode RTI_ENHANCE_DIFFUSE_GAIN (1) or RTI_ENHANCE_SPECULAR (2) -> [P, 3] in
+    out_dtype (float32, int32 or uint8)."""
+    api._require_cuda(lrgb, "lrgb")
+    if lrgb.dim() != 2 or lrgb.shape[0 if planar else 1] != 9:
+        raise ValueError(f"lrgb must be {'[9, P]' if planar else '[P, 9]'}; got {tuple(lrgb.shape)}")
+    out = _enhanced_rgb_out(lrgb, lrgb.shape[1 if planar else 0], out_dtype)
+    return api.relight_lrgb_enhanced_into(lrgb.contiguous(), lu, lv, mode, out, gain=gain, kd=kd, ks=ks, exp=exp,
+                                          layout="planar" if planar else "pixel")
+
+
+@relight_lrgb_enhanced.register_fake
+def _(lrgb, lu, lv, mode, gain=1.0, kd=1.0, ks=0.0, exp=1, planar=False, out_dtype=torch.float32):
+    return lrgb.new_empty((lrgb.shape[1 if planar else 0], 3), dtype=out_dtype)
+
+
+@torch.library.custom_op("rti::relight_lrgb8_enhanced", mutates_args=())
+def relight_lrgb8_enhanced(coef8: torch.Tensor, rgb8: torch.Tensor, qparams: torch.Tensor, lu: float, lv: float,
+                           mode: int, gain: float = 1.0, kd: float = 1.0, ks: float = 0.0, exp: int = 1,
+                           out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """One enhanced RGB rendering of a quantised LRGB map (``rti_relight_lrgb8_enhanced``).  coef8 CUDA uint8
+    [P, 6], rgb8 uint8 [P, 3], qparams fp64 [13] -> [P, 3] in out_dtype (float32, int32 or uint8)."""
+    api._require_cuda(coef8, "coef8")
+    if coef8.dim() != 2 or coef8.shape[1] != 6 or rgb8.dim() != 2 or tuple(rgb8.shape) != (coef8.shape[0], 3):
+        raise ValueError(f"coef8 must be [P, 6] and rgb8 [P, 3]; got {tuple(coef8.shape)} and {tuple(rgb8.shape)}")
+    out = _enhanced_rgb_out(coef8, coef8.shape[0], out_dtype)
+    return api.relight_lrgb8_enhanced_into(coef8.contiguous(), rgb8.contiguous(), qparams.contiguous(), lu, lv, mode,
+                                           out, gain=gain, kd=kd, ks=ks, exp=exp)
+
+
+@relight_lrgb8_enhanced.register_fake
+def _(coef8, rgb8, qparams, lu, lv, mode, gain=1.0, kd=1.0, ks=0.0, exp=1, out_dtype=torch.float32):
+    return coef8.new_empty((coef8.shape[0], 3), dtype=out_dtype)
+
+
+@torch.library.custom_op("rti::relight_rgb8_enhanced", mutates_args=())
+def relight_rgb8_enhanced(coef8: torch.Tensor, qparams: torch.Tensor, lu: float, lv: float, mode: int,
+                          gain: float = 1.0, kd: float = 1.0, ks: float = 0.0, exp: int = 1,
+                          weights: Optional[Sequence[float]] = None,
+                          out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """One enhanced RGB rendering of a quantised RGB PTM (``rti_relight_rgb8_enhanced``).  coef8 CUDA uint8
+    [3, P, 6], qparams fp64 [12], weights None (0.299, 0.587, 0.114) or 3 values -> [P, 3] in out_dtype (float32,
+    int32 or uint8)."""
+    api._require_cuda(coef8, "coef8")
+    out = _enhanced_rgb_out(coef8, _rgb8_pixels(coef8), out_dtype)
+    return api.relight_rgb8_enhanced_into(coef8.contiguous(), qparams.contiguous(), lu, lv, mode, out, gain=gain,
+                                          kd=kd, ks=ks, exp=exp, weights=weights)
+
+
+@relight_rgb8_enhanced.register_fake
+def _(coef8, qparams, lu, lv, mode, gain=1.0, kd=1.0, ks=0.0, exp=1, weights=None, out_dtype=torch.float32):
+    return coef8.new_empty((coef8.shape[1], 3), dtype=out_dtype)
