@@ -135,6 +135,10 @@ class Out:
             self._host = self.t.cpu().numpy()
         return self._host
 
+    def refresh(self):
+        """forget the host copy: the next check reads the device buffer again (an Out used for more than one call)"""
+        self._host = None
+
     def payload(self):
         return self.b.gather(self.host())
 
