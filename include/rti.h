@@ -846,8 +846,8 @@ int     rti_hsh8_normals(const uint8_t* coef8, int basis, int64_t P, const float
  * 16-byte aligned with a channel stride that is a multiple of 4, coef8 8-byte aligned, out aligned as
  * rti_relight_lrgb requires (16 bytes; U8: 4) and normals / kind / peak as rti_ptm_normals requires (16 / 4 / 16);
  * anything else, and the last partial 256-pixel chunk, runs one pixel per lane with the same arithmetic and bits.
- * Not built: planar or strided coef8, a one-pass relight of fp32 RGB maps.  (Diffuse gain and specular rendering
- * from the bytes: rti_relight_rgb8_enhanced, below.) */
+ * Not built: planar or strided coef8.  (Diffuse gain and specular rendering from the bytes:
+ * rti_relight_rgb8_enhanced, below; the fp32 maps themselves in one pass: rti_relight_rgb, below.) */
 int64_t rti_rgb8_qparams_workspace(int64_t P);
 int rti_rgb8_qparams(const float* coef, int coef_layout, int64_t coef_channel_stride, int64_t P,
                      void* workspace, double* qparams, rti_stream_t stream);
@@ -897,8 +897,8 @@ int rti_rgb8_normals(const uint8_t* coef8, int64_t P, const double* qparams, con
  * The vector path (one lane = 4 pixels) applies under the conditions of the plain relight of each form
  * (rti_relight_lrgb, rti_relight_lrgb8, rti_relight_rgb8); anything else, and the last partial 256-pixel chunk, runs
  * one pixel per lane with the same arithmetic and bits.
- * Not built: E > 1 directions per launch, a multi-GPU wrapper, planar RGB output, HSH8 enhanced rendering, enhanced
- * rendering of three fp32 RGB maps in one pass, rti_relight_lrgb8 itself in the table form. */
+ * Not built: E > 1 directions per launch, a multi-GPU wrapper, planar RGB output, HSH8 enhanced rendering,
+ * rti_relight_lrgb8 itself in the table form.  (Three fp32 RGB maps: rti_relight_rgb_enhanced, below.) */
 int rti_relight_lrgb_enhanced(const float* lrgb, int lrgb_layout, int64_t P,
                               int mode, double gain, double kd, double ks, int spec_exp, double lu, double lv,
                               void* out, int out_dtype, rti_stream_t stream);
@@ -909,6 +909,56 @@ int rti_relight_rgb8_enhanced(const uint8_t* coef8, int64_t P, const double* qpa
                               const float* w /* HOST, NULL ok */,
                               int mode, double gain, double kd, double ks, int spec_exp, double lu, double lv,
                               void* out, int out_dtype, rti_stream_t stream);
+
+/* ---- device: three fp32 RGB maps rendered in one pass (rti_rgb.hip) -------------------------------
+ * What rti_fit_shared writes for a colour stack (C = 3), rendered without a detour through 8 bits or LRGB:
+ *   coef: device fp32, three maps of k terms: [c][p][k] (RTI_COEF_PIXEL_MAJOR) or [c][k][p] (RTI_COEF_PLANAR),
+ *         coef_channel_stride in elements, 0 = dense = k·P.  Every offset is formed in 64 bits.
+ * Outputs are RGB interleaved like rti_relight_rgb8's.
+ * rti_relight_rgb: PTM-6, HSH-9 and HSH-16.  out[e][p][c]; luv: device fp64 [E][2].  Per channel and direction
+ *   rti_relight's F32 path: the same basis_eval<float> of ((float)lu, (float)lv) and the same chain acc = a_0·b_0,
+ *   acc = fmaf(a_j, b_j, acc) for j = 1..k−1, converted once (F32; I32 / U8 as rti_relight).  Channel c of the image
+ *   equals rti_relight's of map c bit for bit.  The maps are read once for all E directions of a launch (the kernel
+ *   loops over them): 12k bytes in and 3·sizeof(out) per direction out per pixel.
+ * rti_relight_rgb_enhanced: PTM-6 only.  rti_relight_rgb8_enhanced's definition above with a_cj the fp32 map values
+ *   instead of dequantised bytes: l_j = (wR·r_j + wG·g_j) + wB·b_j in fp32, two products and two sums, no FMA (w:
+ *   three fp32 weights on the HOST, NULL = (0.299f, 0.587f, 0.114f)); the peak, the kind and the normal are those of
+ *   l; diffuse gain: channel c = G(a_c); specular: channel c = kd · D(a_c) + ks · S; kind 4 gives NaN in three
+ *   channels.  out[p][c].  The half vector is formed once on the host and everything travels as kernel arguments.
+ *   With weights (1,0,0), (0,1,0) or (0,0,1) the channel whose weight is 1 equals rti_relight_enhanced's output for
+ *   that map bit for bit; for maps that are dequantised bytes the image equals rti_relight_rgb8_enhanced's.  72 bytes
+ *   in and 3·sizeof(out) out per pixel.
+ * rti_rgb_normals: PTM-6 only.  rti_rgb8_normals on the fp32 maps: the same fp32 luminance, then rti_ptm_normals'
+ *   per-pixel function: normals, kind and peak equal rti_ptm_normals' of that fp32 luminance map bit for bit.  A
+ *   non-finite input value reaches kind 4 here (the bytes of an 8-bit map cannot hold one).  normals: device fp32,
+ *   normal_layout [p][3] or [3][p]; kind: NULL or device uint8 [P]; peak: NULL or device fp32 [P].  72 bytes in and
+ *   12 (+ 1 + 4) out per pixel.
+ * All: device pointers except w, stream-ordered, no allocation, no synchronisation, capturable in a hipGraph; one
+ * launch.  Every argument check answers before any HIP call.  RTI_ERR_BAD_ARG: a null pointer (w, kind and peak may
+ * be null); P < 1 (or E < 1); an unknown basis (as rti_relight answers it); a bad coefficient or normal layout or
+ * mode; a channel stride below dense (a negative one included); non-finite lu, lv, gain, kd, ks or weight; gain < 0;
+ * spec_exp outside [1, 255] in specular mode.  RTI_ERR_UNSUPPORTED: an out_dtype other than F32 / I32 / U8.
+ * PTM-6: the vector path (one lane = 4 pixels, a wave 256, a workgroup 1024; pixel-major rows as coalesced 16-byte
+ * loads through LDS, planar planes as 16-byte loads) needs P % 4 == 0, coef 16-byte aligned with a channel stride
+ * that is a multiple of 4, and out aligned as rti_relight_rgb8 requires (16 bytes; U8: 4) or normals / kind / peak as
+ * rti_rgb8_normals requires (16 / 4 / 16); anything else, and the last partial 256-pixel chunk, runs one pixel per
+ * lane with the same arithmetic and bits.
+ * HSH-9 / HSH-16: a lane owns one pixel, a wave 64 and a workgroup 256, as rti_relight_hsh8 (three channels of four
+ * pixels do not fit a lane's registers).  A full wave of a pixel-major map loads its 64 rows as 16-byte pieces
+ * through LDS if coef is 16-byte aligned with a channel stride that is a multiple of 4, and stores its 192 output
+ * elements as whole dwords if out is 4-byte aligned (U8: and P % 4 == 0); anything else loads and stores per lane,
+ * with the same bits.  The basis rows of up to 64 directions at a time are kept in LDS.
+ * Not built: fp64 RGB maps, planar RGB output, E > 1 for the enhanced entry, diffuse gain for HSH, a multi-GPU
+ * wrapper. */
+int rti_relight_rgb(const float* coef, int basis, int coef_layout, int64_t coef_channel_stride, int64_t P,
+                    const double* luv, int E, void* out, int out_dtype, rti_stream_t stream);
+int rti_relight_rgb_enhanced(const float* coef, int coef_layout, int64_t coef_channel_stride, int64_t P,
+                             const float* w /* HOST, NULL ok */,
+                             int mode, double gain, double kd, double ks, int spec_exp, double lu, double lv,
+                             void* out, int out_dtype, rti_stream_t stream);
+int rti_rgb_normals(const float* coef, int coef_layout, int64_t coef_channel_stride, int64_t P,
+                    const float* w /* HOST, NULL ok */, float* normals, int normal_layout,
+                    uint8_t* kind /* NULL ok */, float* peak /* NULL ok */, rti_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -38,6 +38,7 @@
 #include "rti_lrgb_px.h"
 #include "rti_ptm_px.h"
 #include "rti_quant8.h"
+#include "rti_rgb_px.h"
 #include "rti_stack.h"
 
 namespace rti {
@@ -46,6 +47,9 @@ namespace {
 using namespace lrgb_px;  // K = 6, the wave loads of fp32 maps, the staged row stores
 using hsh_px::dot_k;      // rti_relight's fp32 chain
 using namespace quant8;
+using rgb_px::luminance;  // the fp32 luminance, its normal and the weights: shared with rti_rgb.hip
+using rgb_px::normal_px;
+using rgb_px::Weights;
 
 constexpr int NQ = 2 * K;  // a partial: lo[6], hi[6]; qparams: scale[6], bias[6]
 
@@ -161,16 +165,6 @@ __device__ __forceinline__ void dequantise_px(const uint8_t (&b)[K], const float
   for (int j = 0; j < K; ++j) a[j] = tab[j * TAB + b[j]];
 }
 
-// three channels of a pixel -> the fp32 luminance map: two products and two sums, each rounded
-__device__ __forceinline__ void luminance(const float (&c)[3][K], float wr, float wg, float wb, float (&l)[K]) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    const float rg = wr * c[0][j] + wg * c[1][j];
-    l[j] = rg + wb * c[2][j];
-  }
-}
-
 // ---- kernels ------------------------------------------------------------------------------------------------------
 // All: a wave owns pixels [wave_px, wave_px + 256), as rti_lrgb8.hip's kernels.
 
@@ -273,20 +267,6 @@ relight_rgb8_k(const uint8_t* __restrict__ coef8, int64_t P, int vec, const doub
       for (int ch = 0; ch < 3; ++ch) px[ch] = o[ch];
     }
   }
-}
-
-struct Weights {
-  float r, g, b;
-};
-
-// 18 bytes of a pixel -> what rti_ptm_normals writes for its fp32 luminance coefficients
-__device__ __forceinline__ ptm_px::NormalOut normal_px(const float (&c)[3][K], const Weights& w, bool want_peak) {
-  float l[K];
-  luminance(c, w.r, w.g, w.b, l);
-  double a[K];
-#pragma unroll
-  for (int j = 0; j < K; ++j) a[j] = (double)l[j];
-  return ptm_px::normal_of(a, want_peak);
 }
 
 template <int NL>
@@ -497,9 +477,8 @@ extern "C" int rti_rgb8_normals(const uint8_t* coef8, int64_t P, const double* q
   if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", E);
   if (normal_layout != RTI_NORMAL_PIXEL_MAJOR && normal_layout != RTI_NORMAL_PLANAR)
     return fail(RTI_ERR_BAD_ARG, "%s: normal layout %d", E, normal_layout);
-  const Weights wt{w ? w[0] : 0.299f, w ? w[1] : 0.587f, w ? w[2] : 0.114f};
-  if (!std::isfinite(wt.r) || !std::isfinite(wt.g) || !std::isfinite(wt.b))
-    return fail(RTI_ERR_BAD_ARG, "%s: non-finite weight", E);
+  Weights wt;
+  if (int st = rgb_px::host_weights(E, w, wt)) return st;
   if (!aligned_to(qparams, 8)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 8-byte aligned", E);
   const int vec = P % 4 == 0 && aligned_to(coef8, 8) && aligned_to(normals, 16) && (!kind || aligned_to(kind, 4)) &&
                           (!peak || aligned_to(peak, 16))
@@ -522,9 +501,8 @@ extern "C" int rti_relight_rgb8_enhanced(const uint8_t* coef8, int64_t P, const 
   if (int st = check_pointers(E, {coef8, qparams, out})) return st;
   if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", E);
   if (int st = enhance_px::check_enhance(E, mode, gain, kd, ks, spec_exp, lu, lv)) return st;
-  const Weights wt{w ? w[0] : 0.299f, w ? w[1] : 0.587f, w ? w[2] : 0.114f};
-  if (!std::isfinite(wt.r) || !std::isfinite(wt.g) || !std::isfinite(wt.b))
-    return fail(RTI_ERR_BAD_ARG, "%s: non-finite weight", E);
+  Weights wt;
+  if (int st = rgb_px::host_weights(E, w, wt)) return st;
   if (int st = enhance_px::check_enhance_out(E, out_dtype)) return st;
   if (!aligned_to(qparams, 8)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 8-byte aligned", E);
   const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // a lane's dword / the wave's 16-byte pieces

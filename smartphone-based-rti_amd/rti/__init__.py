@@ -39,6 +39,11 @@ bara96/Smartphone-based-RTI: analysis.py:196-411, interactive_relighting.py:11-3
     rgb = rti.relight_rgb8_enhanced(p, 0.3, -0.2, "specular", kd=0.4, ks=150, exp=75, out_dtype=torch.uint8)
     rgb = rti.relight_lrgb8_enhanced(q, 0.3, -0.2, "diffuse_gain", gain=3.5)      # and relight_lrgb_enhanced(m, ...)
 
+    c3 = rti.fit(Irgb, lu, lv)                       # the three fp32 maps themselves, [3, H, W, 6], in one launch each:
+    rgb = rti.relight_rgb(c3, 0.3, -0.2, out_dtype=torch.uint8)   # [H, W, 3]; also basis="hsh9" / "hsh16"
+    rgb = rti.relight_rgb_enhanced(c3, 0.3, -0.2, "diffuse_gain", gain=3.5)       # nothing quantised or compressed
+    n = rti.rgb_normals(c3)                          # normals of the fp32 luminance
+
 Compute runs in HIP kernels of librti.so (include/rti.h); importing this
 package does not touch the GPU.
 """
@@ -59,7 +64,9 @@ from .api import (BASES, FitAccumulator, apply_operator, basis_eval, basis_id, b
                   QuantisedRGB, dequantise_rgb, quantise_rgb, relight_rgb8, relight_rgb8_into, rgb8_normals,
                   rgb8_normals_into, rgb8_qparams_into, rgb8_qparams_workspace, rgb8_quantise_into,
                   relight_lrgb_enhanced, relight_lrgb_enhanced_into, relight_lrgb8_enhanced,
-                  relight_lrgb8_enhanced_into, relight_rgb8_enhanced, relight_rgb8_enhanced_into)
+                  relight_lrgb8_enhanced_into, relight_rgb8_enhanced, relight_rgb8_enhanced_into,
+                  relight_rgb, relight_rgb_into, relight_rgb_enhanced, relight_rgb_enhanced_into, rgb_normals,
+                  rgb_normals_into)
 from .io import read_ptm, read_ptm8, read_rti, write_ptm, write_rti
 
 __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_into", "fit_chunked",
@@ -79,7 +86,8 @@ __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_in
            "dequantise_rgb", "quantise_rgb", "relight_rgb8", "relight_rgb8_into", "rgb8_normals", "rgb8_normals_into",
            "rgb8_qparams_into", "rgb8_qparams_workspace", "rgb8_quantise_into", "relight_lrgb_enhanced",
            "relight_lrgb_enhanced_into", "relight_lrgb8_enhanced", "relight_lrgb8_enhanced_into",
-           "relight_rgb8_enhanced", "relight_rgb8_enhanced_into", "read_ptm", "read_ptm8", "write_ptm",
+           "relight_rgb8_enhanced", "relight_rgb8_enhanced_into", "relight_rgb", "relight_rgb_into",
+           "relight_rgb_enhanced", "relight_rgb_enhanced_into", "rgb_normals", "rgb_normals_into", "read_ptm", "read_ptm8", "write_ptm",
            "read_rti", "write_rti", "library_path", "load"]
 
 __version__ = "0.1.0"

@@ -192,6 +192,12 @@ SIGNATURES = {
                                             _c_double, _c_int, _c_double, _c_double, _c_void_p, _c_int, _c_void_p]),
     "rti_relight_rgb8_enhanced": (_c_int, [_c_void_p, _c_i64, _c_void_p, _c_void_p, _c_int, _c_double, _c_double,
                                            _c_double, _c_int, _c_double, _c_double, _c_void_p, _c_int, _c_void_p]),
+    "rti_relight_rgb": (_c_int, [_c_void_p, _c_int, _c_int, _c_i64, _c_i64, _c_void_p, _c_int, _c_void_p, _c_int,
+                                 _c_void_p]),
+    "rti_relight_rgb_enhanced": (_c_int, [_c_void_p, _c_int, _c_i64, _c_i64, _c_void_p, _c_int, _c_double, _c_double,
+                                          _c_double, _c_int, _c_double, _c_double, _c_void_p, _c_int, _c_void_p]),
+    "rti_rgb_normals": (_c_int, [_c_void_p, _c_int, _c_i64, _c_i64, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p,
+                                 _c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -2184,6 +2184,135 @@ def relight_rgb8_enhanced(q, lu, lv, mode, *, gain=1.0, kd=1.0, ks=0.0, exp=1, o
                                       weights=weights)
 
 
+# ---- three fp32 RGB maps rendered in one pass (rti_rgb.hip) -------------------
+
+def _ptm_only(basis, what):
+    """The basis of an entry that reads PTM-6 maps alone; anything else is not built."""
+    if basis_id(basis) != L.RTI_BASIS_PTM6:
+        raise NotImplementedError(f"{what} reads PTM-6 maps only; got basis {basis!r}")
+
+
+class _RGBMaps:
+    """What ``_relight8`` asks of its map, for three fp32 maps: the device and the spatial shape."""
+    __slots__ = ("device", "shape")
+
+    def __init__(self, device, shape):
+        self.device, self.shape = device, tuple(shape)
+
+
+def _rgb_spatial(coef, k, cl, name="coef"):
+    """Three maps [3, ..., k] (pixel-major) or [3, k, ...] (planar) -> their spatial shape."""
+    _require_cuda(coef, name)
+    if coef.dtype != torch.float32:
+        raise ValueError(f"{name} must be float32; got {coef.dtype}")
+    if coef.dim() < 3 or coef.shape[0] != 3:
+        raise ValueError(f"{name} must be three maps of {k} terms per pixel, [3, ...]; got {tuple(coef.shape)}")
+    return _coef_spatial(coef[0], k, cl)
+
+
+def relight_rgb_into(coef, luv_dev, out, *, basis="ptm", layout="pixel"):
+    """Launch ``rti_relight_rgb`` on preallocated tensors (no allocation, graph-capturable).
+
+    coef: contiguous CUDA fp32 [3, P, k] (layout="pixel") or [3, k, P] ("planar"), any spatial shape in place of P,
+    as ``fit`` returns it for a [3, N, H, W] stack; basis "ptm", "hsh9" or "hsh16"; luv_dev: CUDA fp64 [E, 2]; out:
+    float32, int32 or uint8 with E·P·3 elements ([E, P, 3], RGB interleaved)."""
+    b = basis_id(basis)
+    P = _hsh_maps(coef, basis_terms(b))
+    luv, E = _luv_arg(luv_dev, coef)
+    odt = _out8_dtype(out)
+    st = L.lib().rti_relight_rgb(_vp(coef), b, _layout_id(layout), 0, P, luv, E,
+                                 _map_out(out, "out", out.dtype, E * P * 3, coef), odt, _stream_of(coef))
+    L.check(st, "rti_relight_rgb")
+    return out
+
+
+def relight_rgb_enhanced_into(coef, lu, lv, mode, out, *, gain=1.0, kd=1.0, ks=0.0, exp=1, layout="pixel",
+                              weights=None, basis="ptm"):
+    """Launch ``rti_relight_rgb_enhanced`` on preallocated tensors (no allocation, graph-capturable).
+
+    coef: contiguous CUDA fp32 PTM-6 maps [3, P, 6] / [3, 6, P] as ``relight_rgb_into``; weights as
+    ``rgb8_normals_into``; the rest as ``relight_lrgb_enhanced_into``: out float32, int32 or uint8 with P·3
+    elements ([P, 3])."""
+    _ptm_only(basis, "rti_relight_rgb_enhanced")
+    P = _rgb_maps(coef)
+    odt = _out8_dtype(out)
+    st = L.lib().rti_relight_rgb_enhanced(_vp(coef), _layout_id(layout), 0, P, _luma_weights(weights),
+                                          *_enhance_scalars(mode, gain, kd, ks, exp, lu, lv),
+                                          _map_out(out, "out", out.dtype, P * 3, coef), odt, _stream_of(coef))
+    L.check(st, "rti_relight_rgb_enhanced")
+    return out
+
+
+def rgb_normals_into(coef, normals, kind=None, peak=None, *, layout="pixel", normal_layout="pixel", weights=None,
+                     basis="ptm"):
+    """Launch ``rti_rgb_normals`` on preallocated tensors (no allocation, graph-capturable).
+
+    coef as ``relight_rgb_enhanced_into``; normals: fp32 with 3 values per pixel, [P, 3] (normal_layout="pixel")
+    or [3, P]; kind: uint8 [P] or None; peak: fp32 [P] or None; weights: None (0.299, 0.587, 0.114) or three
+    values (R, G, B)."""
+    _ptm_only(basis, "rti_rgb_normals")
+    P = _rgb_maps(coef)
+    st = L.lib().rti_rgb_normals(_vp(coef), _layout_id(layout), 0, P, _luma_weights(weights),
+                                 _map_out(normals, "normals", torch.float32, 3 * P, coef),
+                                 _normal_layout_id(normal_layout),
+                                 None if kind is None else _map_out(kind, "kind", torch.uint8, P, coef),
+                                 None if peak is None else _map_out(peak, "peak", torch.float32, P, coef),
+                                 _stream_of(coef))
+    L.check(st, "rti_rgb_normals")
+    return normals
+
+
+def relight_rgb(coef, lu, lv, basis="ptm", *, layout="pixel", out_dtype=torch.float32):
+    """Relight the three fp32 maps of a colour fit to RGB images on the GPU in one launch (``rti_relight_rgb``),
+    reading the maps once for every direction.  Channel c of the images equals ``relight(coef[c], lu, lv, basis)``
+    bit for bit.
+
+    coef: CUDA fp32 [3, H, W, k] / [3, P, k] (layout="pixel") or [3, k, H, W] / [3, k, P] ("planar"), as ``fit``
+    returns it for a [3, N, H, W] stack; basis "ptm", "hsh9" or "hsh16".  lu, lv: scalars or E directions.
+    Returns [E, H, W, 3], squeezed to [H, W, 3] for scalar directions, in out_dtype: float32, or int32 / uint8
+    converted as ``relight`` does."""
+    b = basis_id(basis)
+    cl = _layout_id(layout)
+    spatial = _rgb_spatial(coef, basis_terms(b), cl)
+    m = coef.contiguous()
+    return _relight8(_RGBMaps(m.device, spatial), lu, lv, out_dtype,
+                     lambda luv_d, out: relight_rgb_into(m, luv_d, out, basis=b, layout=cl))
+
+
+def relight_rgb_enhanced(coef, lu, lv, mode, *, gain=1.0, kd=1.0, ks=0.0, exp=1, layout="pixel",
+                         out_dtype=torch.float32, weights=None, basis="ptm"):
+    """One enhanced RGB rendering of the three fp32 PTM-6 maps of a colour fit at (lu, lv) on the GPU in one launch
+    (``rti_relight_rgb_enhanced``), without quantising them or compressing them to LRGB.  The peak and the normal
+    are those of the luminance ``rgb_normals`` reads (weights: None = 0.299, 0.587, 0.114, or three values); every
+    channel keeps its own coefficients.
+
+    mode="diffuse_gain": each channel's curvature scaled by ``gain`` about the luminance's peak.  mode="specular":
+    kd·L_c(lu, lv) + ks·max(0, n·H)^exp.  coef as ``relight_rgb`` with 6 terms; any other basis raises
+    NotImplementedError.  Returns [H, W, 3] in out_dtype.  With a unit weight on channel c, that channel is
+    ``relight_enhanced(coef[c], ...)`` bit for bit."""
+    _ptm_only(basis, "rti_relight_rgb_enhanced")
+    cl = _layout_id(layout)
+    spatial = _rgb_spatial(coef, 6, cl)
+    out = _enhanced_rgb_out(spatial, out_dtype, coef.device)
+    return relight_rgb_enhanced_into(coef.contiguous(), lu, lv, mode, out, gain=gain, kd=kd, ks=ks, exp=exp,
+                                     layout=cl, weights=weights)
+
+
+def rgb_normals(coef, *, layout="pixel", normal_layout="pixel", weights=None, return_kind=False, return_peak=False,
+                basis="ptm"):
+    """Per-pixel surface normals of the three fp32 PTM-6 maps of a colour fit on the GPU (``rti_rgb_normals``): with
+    l = (w0·r + w1·g) + w2·b formed in float32, ``normals(l, ...)`` bit for bit, without building l.
+
+    coef as ``relight_rgb`` with 6 terms (any other basis raises NotImplementedError); weights: None (0.299,
+    0.587, 0.114) or three values.  Returns what ``normals`` returns."""
+    _ptm_only(basis, "rti_rgb_normals")
+    cl, nl = _layout_id(layout), _normal_layout_id(normal_layout)
+    spatial = _rgb_spatial(coef, 6, cl)
+    n, kind, peak = _normal_outputs(spatial, nl, return_kind, return_peak, coef.device)
+    rgb_normals_into(coef.contiguous(), n, kind, peak, layout=cl, normal_layout=nl, weights=weights)
+    return _normal_results(n, kind, peak, spatial, nl)
+
+
 # ---- light operators (RBF, fused PTM/HSH fit + evaluation) ----------------------------------
 
 def _query(qu, qv):

@@ -3,7 +3,7 @@
 ``relight_enhanced`` / ``map_unsharp`` / ``shade_normals`` / ``lrgb_from_rgb`` / ``relight_lrgb`` /
 ``lrgb_quantise`` / ``relight_lrgb8`` / ``hsh_quantise`` / ``relight_hsh8`` / ``hsh_normals`` / ``hsh8_normals`` /
 ``rgb8_quantise`` / ``relight_rgb8`` / ``rgb8_normals`` / ``relight_lrgb_enhanced`` / ``relight_lrgb8_enhanced`` /
-``relight_rgb8_enhanced``.
+``relight_rgb8_enhanced`` / ``relight_rgb`` / ``relight_rgb_enhanced`` / ``rgb_normals``.
 
 They let the fit and relight kernels sit inside torch programs (and
 ``torch.library`` fake-tensor tracing) while the compute stays in librti's
@@ -660,3 +660,66 @@ def relight_rgb8_enhanced(coef8: torch.Tensor, qparams: torch.Tensor, lu: float,
 @relight_rgb8_enhanced.register_fake
 def _(coef8, qparams, lu, lv, mode, gain=1.0, kd=1.0, ks=0.0, exp=1, weights=None, out_dtype=torch.float32):
     return coef8.new_empty((coef8.shape[1], 3), dtype=out_dtype)
+
+
+# ---- three fp32 RGB maps rendered in one pass -------------------------------
+
+def _rgb_pixels(coef, k, planar):
+    api._require_cuda(coef, "coef")
+    if coef.dim() != 3 or coef.shape[0] != 3 or coef.shape[1 if planar else 2] != k:
+        raise ValueError(f"coef must be {f'[3, {k}, P]' if planar else f'[3, P, {k}]'}; got {tuple(coef.shape)}")
+    return coef.shape[2 if planar else 1]
+
+
+@torch.library.custom_op("rti::relight_rgb", mutates_args=())
+def relight_rgb(coef: torch.Tensor, luv: torch.Tensor, basis: int = L.RTI_BASIS_PTM6, planar: bool = False,
+                out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """RGB images of three fp32 maps (``rti_relight_rgb``).  coef CUDA fp32 [3, P, k] (or [3, k, P] if planar),
+    basis PTM-6, HSH-9 or HSH-16, luv [E, 2] -> [E, P, 3] in out_dtype (float32, int32 or uint8)."""
+    P = _rgb_pixels(coef, api.basis_terms(basis), planar)
+    if out_dtype not in api._ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    luv_d = luv.detach().to(device=coef.device, dtype=torch.float64).contiguous()
+    out = coef.new_empty((luv.shape[0], P, 3), dtype=out_dtype)
+    return api.relight_rgb_into(coef.contiguous(), luv_d, out, basis=basis, layout="planar" if planar else "pixel")
+
+
+@relight_rgb.register_fake
+def _(coef, luv, basis=L.RTI_BASIS_PTM6, planar=False, out_dtype=torch.float32):
+    return coef.new_empty((luv.shape[0], coef.shape[2 if planar else 1], 3), dtype=out_dtype)
+
+
+@torch.library.custom_op("rti::relight_rgb_enhanced", mutates_args=())
+def relight_rgb_enhanced(coef: torch.Tensor, lu: float, lv: float, mode: int, gain: float = 1.0, kd: float = 1.0,
+                         ks: float = 0.0, exp: int = 1, planar: bool = False,
+                         weights: Optional[Sequence[float]] = None,
+                         out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """One enhanced RGB rendering of three fp32 PTM-6 maps (``rti_relight_rgb_enhanced``).  coef CUDA fp32
+    [3, P, 6] (or [3, 6, P] if planar), weights None (0.299, 0.587, 0.114) or 3 values -> [P, 3] in out_dtype
+    (float32, int32 or uint8)."""
+    out = _enhanced_rgb_out(coef, _rgb_pixels(coef, 6, planar), out_dtype)
+    return api.relight_rgb_enhanced_into(coef.contiguous(), lu, lv, mode, out, gain=gain, kd=kd, ks=ks, exp=exp,
+                                         layout="planar" if planar else "pixel", weights=weights)
+
+
+@relight_rgb_enhanced.register_fake
+def _(coef, lu, lv, mode, gain=1.0, kd=1.0, ks=0.0, exp=1, planar=False, weights=None, out_dtype=torch.float32):
+    return coef.new_empty((coef.shape[2 if planar else 1], 3), dtype=out_dtype)
+
+
+@torch.library.custom_op("rti::rgb_normals", mutates_args=())
+def rgb_normals(coef: torch.Tensor, planar: bool = False, normals_planar: bool = False,
+                weights: Optional[Sequence[float]] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Surface normals of three fp32 PTM-6 maps (``rti_rgb_normals``).  coef CUDA fp32 [3, P, 6] (or [3, 6, P] if
+    planar), weights None (0.299, 0.587, 0.114) or 3 values -> ``(normals, kind, peak)``: normals fp32 [P, 3] (or
+    [3, P] if normals_planar), kind uint8 [P], peak fp32 [P]."""
+    P = _rgb_pixels(coef, 6, planar)
+    normals, kind, peak = _normal_triple(coef, P, normals_planar)
+    api.rgb_normals_into(coef.contiguous(), normals, kind, peak, layout="planar" if planar else "pixel",
+                         normal_layout="planar" if normals_planar else "pixel", weights=weights)
+    return normals, kind, peak
+
+
+@rgb_normals.register_fake
+def _(coef, planar=False, normals_planar=False, weights=None):
+    return _normal_triple(coef, coef.shape[2 if planar else 1], normals_planar)
