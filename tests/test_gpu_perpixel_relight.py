@@ -214,13 +214,23 @@ def test_compat_compute_end_to_end(cuda, tmp_path, ptm):
 
 @pytest.mark.parametrize("basis", ["ptm", "hsh9", "hsh"])
 @pytest.mark.parametrize("cdt", [torch.float32, torch.float64])
-def test_relight_staged_rows_bit_identical_to_planar(cuda, basis, cdt):
-    """Pixel-major maps go through the LDS-staged coalesced row loads (whole 256-pixel wave chunks),
-    planar maps through per-lane loads; both evaluate the same products in the same order, so over a
-    large image (thousands of workgroups, a partial last chunk) the outputs are bit-identical —
-    for relight (several evals, every output type) and for the interactive frame."""
+@pytest.mark.parametrize("P", [1_000_037, 1_000_036])
+def test_relight_staged_rows_bit_identical_to_planar(cuda, basis, cdt, P):
+    """Pixel-major and planar maps evaluate the same products in the same order, so over a large image
+    (thousands of workgroups, a partial last chunk) the outputs are bit-identical — for relight
+    (several evals, every output type) and for the interactive frame.  Which loads run depends on P:
+
+    P = 1 000 037 (P % 4 = 1): rti_relight takes one pixel per lane for both layouts, per-lane loads
+    and scalar stores over thousands of workgroups.  The frame kernel stages whatever P % 4 is:
+    pixel-major maps whose rows fit the LDS slab (fp32 PTM-6 and HSH-9, fp64 PTM-6) go through the
+    coalesced row loads in whole 256-pixel wave chunks, with a ragged tail of 101 pixels, one of them
+    alone in its lane.
+    P = 1 000 036 (P % 4 = 0, P % 256 = 100): rti_relight takes four pixels per lane and vector stores;
+    the same pixel-major maps go through the staged row loads, the last chunk of 100 pixels and the
+    planar maps through per-lane loads.
+
+    tests/test_gpu_relight_paths.py holds the same paths to an outside reference at small sizes."""
     k = rti.basis_terms(basis)
-    P = 1_000_037
     g = torch.Generator(device=cuda).manual_seed(11)
     coef = (torch.rand((P, k), generator=g, device=cuda, dtype=torch.float64) * 120 - 60).to(cdt)
     coef[:, 0 if basis != "ptm" else 5] += 140
