@@ -948,8 +948,8 @@ int rti_relight_rgb8_enhanced(const uint8_t* coef8, int64_t P, const double* qpa
  * through LDS if coef is 16-byte aligned with a channel stride that is a multiple of 4, and stores its 192 output
  * elements as whole dwords if out is 4-byte aligned (U8: and P % 4 == 0); anything else loads and stores per lane,
  * with the same bits.  The basis rows of up to 64 directions at a time are kept in LDS.
- * Not built: fp64 RGB maps, planar RGB output, E > 1 for the enhanced entry, diffuse gain for HSH, a multi-GPU
- * wrapper. */
+ * Not built: fp64 RGB maps, planar RGB output, diffuse gain for HSH, a multi-GPU wrapper.  (Several directions per
+ * launch of an enhanced rendering: rti_relight_hsh_specular, below, for HSH maps.) */
 int rti_relight_rgb(const float* coef, int basis, int coef_layout, int64_t coef_channel_stride, int64_t P,
                     const double* luv, int E, void* out, int out_dtype, rti_stream_t stream);
 int rti_relight_rgb_enhanced(const float* coef, int coef_layout, int64_t coef_channel_stride, int64_t P,
@@ -959,6 +959,62 @@ int rti_relight_rgb_enhanced(const float* coef, int coef_layout, int64_t coef_ch
 int rti_rgb_normals(const float* coef, int coef_layout, int64_t coef_channel_stride, int64_t P,
                     const float* w /* HOST, NULL ok */, float* normals, int normal_layout,
                     uint8_t* kind /* NULL ok */, float* peak /* NULL ok */, rti_stream_t stream);
+
+/* ---- device: specular enhancement of HSH maps under a normal map (rti_hsh_specular.hip) -----------
+ * The specular mode of rti_relight_enhanced for the bases without a closed-form peak.  An HSH normal is a search
+ * (rti_hsh_normals, once per object), so these entries read a normal map (rti_hsh_normals / rti_hsh8_normals, optionally
+ * sharpened by rti_map_unsharp) instead of recomputing the normal per frame; the semantics are build-defined.  Per
+ * pixel p, channel c and direction e, every operation rounded, each expression left to right as written:
+ *   V_c  = rti_relight's F32 value of channel c's coefficients at (lu_e, lv_e), bit for bit: the same
+ *          basis_eval<float> of ((float)lu, (float)lv) and the same chain acc = c_0·b_0, acc = fmaf(c_j, b_j, acc) for
+ *          j = 1..k−1; for the 8-bit map c_j = (float)raw_j·step_j + bias_j as rti_relight_hsh8 states it
+ *   h    = n_x·hx + n_y·hy + n_z·hz           fp64 from the fp32 normal; H = (hx, hy, hz) = (lu, lv, lw + 1)/‖·‖ with
+ *                                             lw = sqrt(max(0, 1 − lu² − lv²)), formed on the HOST in fp64 exactly as
+ *                                             rti_shade_normals forms it
+ *   S    = ks · max(0, h)^spec_exp            rti_relight_enhanced's repeated squaring
+ *   v_c  = kd·(double)V_c + S                 fp64, no contraction
+ *   out  = NaN if n_x, n_y or n_z is NaN, else v_c; converted once (F32; I32 / U8 as rti_relight)
+ * The highlight is white: one S for the three channels.  A NaN normal (kind 4 of the normal entries) gives a NaN
+ * pixel whatever ks is; a non-finite coefficient propagates through V_c as in rti_relight.  There is no albedo
+ * argument: the diffuse term is the HSH value itself.  With kd = 1, ks = 0 and finite normals the F32 image equals
+ * rti_relight's (rti_relight_rgb's, rti_relight_hsh8's) as values (a −0 becomes +0); with kd = 0, finite coefficients
+ * and C = 1 it equals rti_shade_normals(kd = 0) bit for bit.
+ * rti_relight_hsh_specular: coef: device fp32, C = 1 or 3 maps as rti_hsh_normals takes them: [c][p][k]
+ *   (RTI_COEF_PIXEL_MAJOR) or [c][k][p] (RTI_COEF_PLANAR), coef_channel_stride in elements, 0 = dense = k·P (one map
+ *   never uses it).  out[e][p] for C = 1, out[e][p][c] (RGB interleaved) for C = 3.  4·C·k + 12 bytes in and
+ *   C·sizeof(out) per direction out per pixel.
+ * rti_relight_hsh8_specular: coef8 / qparams as rti_relight_hsh8 takes them; out[e][p][c].  The image equals
+ *   rti_relight_hsh_specular's of the dequantised maps bit for bit.  3k + 12 bytes in and 3·sizeof(out) per
+ *   direction out per pixel.
+ * Both: normals: device fp32, normal_layout [p][3] or [3][p].  luv: [E][2] fp64 on the HOST, 1 <= E <=
+ *   RTI_SPECULAR_MAX_DIRS -- unlike rti_relight_hsh8's device luv: the entry forms each direction's
+ *   {lu, lv, hx, hy, hz} in fp64 and all of them travel as one kernel argument (16 × 40 bytes), so a call allocates
+ *   and copies nothing and can be captured in a hipGraph (the directions are then part of the capture).  One launch;
+ *   the coefficients or bytes and the normal are read once for all E directions.  Device pointers otherwise,
+ *   stream-ordered, no synchronisation.
+ * Every argument check answers before any HIP call.  RTI_ERR_BAD_ARG: a null pointer; P < 1; E outside
+ * [1, RTI_SPECULAR_MAX_DIRS]; C other than 1 or 3; a channel stride below dense (C = 3); a bad coefficient or normal
+ * layout; non-finite kd, ks or luv value; spec_exp outside [1, 255]; qparams off 4 bytes.  RTI_ERR_UNSUPPORTED: a basis
+ * other than HSH-9 / HSH-16 (PTM-6 has rti_relight_rgb_enhanced); an out_dtype other than F32 / I32 / U8.
+ * One pixel per lane, 64 consecutive pixels per wave, as rti_relight_hsh8.  The fast paths move a full wave's
+ * contiguous run as whole 16-byte (output images: 4-byte) pieces through LDS and need:
+ *   the fp32 maps, pixel-major:  coef 16-byte aligned and (C = 3) a channel stride that is a multiple of 4
+ *                                (planar maps are read per lane, coalesced as they are);
+ *   coef8:                       16-byte aligned;
+ *   normals, pixel-major:        16-byte aligned (planar normals are read per lane);
+ *   out:                         4-byte aligned, and for U8 also P % 4 == 0.
+ * Anything else, and the last partial wave of any launch, loads and stores per lane through the same per-pixel
+ * function and gives the same bits.
+ * Not built: diffuse gain for HSH, planar RGB output, a multi-GPU wrapper. */
+#define RTI_SPECULAR_MAX_DIRS 16
+int rti_relight_hsh_specular(const float* coef, int basis, int coef_layout, int C, int64_t coef_channel_stride,
+                             int64_t P, const float* normals, int normal_layout,
+                             double kd, double ks, int spec_exp, const double* luv /* HOST [E][2] */, int E,
+                             void* out, int out_dtype, rti_stream_t stream);
+int rti_relight_hsh8_specular(const uint8_t* coef8, int basis, int64_t P, const float* qparams,
+                              const float* normals, int normal_layout,
+                              double kd, double ks, int spec_exp, const double* luv /* HOST [E][2] */, int E,
+                              void* out, int out_dtype, rti_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -2313,6 +2313,155 @@ def rgb_normals(coef, *, layout="pixel", normal_layout="pixel", weights=None, re
     return _normal_results(n, kind, peak, spatial, nl)
 
 
+# ---- specular enhancement of HSH maps under a normal map (rti_hsh_specular.hip) -
+
+def _specular_basis(basis):
+    """A basis name or id -> the id of HSH-9 or HSH-16; PTM-6 has entries of its own."""
+    b = basis_id(basis)
+    if b not in _HSH8_NAMES:
+        raise NotImplementedError(f"relight_hsh_specular reads HSH-9 and HSH-16 maps only; got basis {basis!r} "
+                                  "(PTM-6 maps: relight_rgb_enhanced, relight_enhanced)")
+    return b
+
+
+def _specular_dirs(lu, lv):
+    """Scalars or up to RTI_SPECULAR_MAX_DIRS directions -> (host fp64 [E, 2], whether they were scalars)."""
+    scalar = np.ndim(lu) == 0 and np.ndim(lv) == 0
+    u, v = (np.asarray(x.detach().cpu() if torch.is_tensor(x) else x, np.float64).ravel() for x in (lu, lv))
+    if u.size != v.size or u.size == 0:
+        raise ValueError(f"lu and lv must hold the same number of directions, at least one; got {u.size} and {v.size}")
+    if u.size > L.RTI_SPECULAR_MAX_DIRS:
+        raise ValueError(f"at most {L.RTI_SPECULAR_MAX_DIRS} directions per launch; got {u.size} (call once per "
+                         f"{L.RTI_SPECULAR_MAX_DIRS})")
+    return np.ascontiguousarray(np.stack([u, v], -1)), scalar
+
+
+def _specular_normals(n, like):
+    """A contiguous CUDA fp32 normal map on like's device -> P."""
+    if not torch.is_tensor(n) or n.dtype != torch.float32 or not n.is_contiguous() or n.numel() == 0 or n.numel() % 3:
+        raise ValueError("n must be a contiguous float32 normal map of 3 values per pixel; got "
+                         f"{getattr(n, 'dtype', type(n))} {tuple(getattr(n, 'shape', ()))}")
+    _require_cuda(n, "n")
+    if n.device != like.device:
+        raise ValueError(f"n is on {n.device}, the coefficients on {like.device}")
+    return n.numel() // 3
+
+
+def relight_hsh_specular_into(coef, n, lu, lv, out, *, basis="hsh16", kd=1.0, ks=0.0, exp=1, layout="pixel",
+                              normal_layout="pixel"):
+    """Launch ``rti_relight_hsh_specular`` on preallocated tensors (no allocation, no copy, graph-capturable: the
+    directions travel as kernel arguments and become part of a capture).
+
+    coef: contiguous CUDA fp32, one map [P, k] (layout="pixel") or [k, P] ("planar"), or three [3, P, k] /
+    [3, k, P], any spatial shape in place of P; n: contiguous fp32 normals [P, 3] or [3, P]; lu, lv: scalars or up
+    to 16 directions on the host; out: float32, int32 or uint8 with E·P elements ([E, P]) for one map, E·P·3
+    ([E, P, 3], RGB interleaved) for three.  P is n's pixel count."""
+    b = _specular_basis(basis)
+    k = _HSH8_TERMS[b]
+    _require_cuda(coef, "coef")
+    P = _specular_normals(n, coef)
+    if coef.dtype != torch.float32 or not coef.is_contiguous() or coef.numel() not in (P * k, 3 * P * k):
+        raise ValueError(f"coef must be contiguous float32 with {k} or 3·{k} terms for each of n's {P} pixels; got "
+                         f"{coef.dtype} {tuple(coef.shape)}")
+    C = coef.numel() // (P * k)
+    luv, _ = _specular_dirs(lu, lv)
+    E = luv.shape[0]
+    odt = _out8_dtype(out)
+    st = L.lib().rti_relight_hsh_specular(_vp(coef), b, _layout_id(layout), C, 0, P, _vp(n),
+                                          _normal_layout_id(normal_layout), float(kd), float(ks), int(exp),
+                                          _dptr(luv), E, _map_out(out, "out", out.dtype, E * P * C, coef), odt,
+                                          _stream_of(coef))
+    L.check(st, "rti_relight_hsh_specular")
+    return out
+
+
+def relight_hsh8_specular_into(coef8, qparams, n, lu, lv, out, *, basis="hsh16", kd=1.0, ks=0.0, exp=1,
+                               normal_layout="pixel"):
+    """Launch ``rti_relight_hsh8_specular`` on preallocated tensors (no allocation, no copy, graph-capturable).
+
+    coef8: contiguous CUDA uint8 [P, 3, k], any spatial shape in place of P; qparams: CUDA fp32 [2k]; n, lu, lv
+    as ``relight_hsh_specular_into``; out: float32, int32 or uint8 with E·P·3 elements ([E, P, 3])."""
+    b = _specular_basis(basis)
+    k = _HSH8_TERMS[b]
+    P = _bytes_map(coef8, 3 * k, f"{3 * k} bytes")
+    if _specular_normals(n, coef8) != P:
+        raise ValueError(f"n has {n.numel() // 3} pixels, coef8 {P}")
+    luv, _ = _specular_dirs(lu, lv)
+    E = luv.shape[0]
+    odt = _out8_dtype(out)
+    st = L.lib().rti_relight_hsh8_specular(_vp(coef8), b, P, _qparams_arg(qparams, torch.float32, 2 * k, coef8),
+                                           _vp(n), _normal_layout_id(normal_layout), float(kd), float(ks), int(exp),
+                                           _dptr(luv), E, _map_out(out, "out", out.dtype, E * P * 3, coef8), odt,
+                                           _stream_of(coef8))
+    L.check(st, "rti_relight_hsh8_specular")
+    return out
+
+
+def _specular_frame(n, nl, spatial, E, rgb, out_dtype, device):
+    """What the two specular renderers do before their launch: n's pixels against the map's, and the output ->
+    (n contiguous, out [E, *spatial(, 3)])."""
+    if out_dtype not in _ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    if not torch.is_tensor(n) or n.dtype != torch.float32:
+        raise ValueError(f"n must be a float32 normal map; got {getattr(n, 'dtype', type(n))}")
+    _require_cuda(n, "n")
+    if _coef_spatial(n, 3, nl) != tuple(spatial):
+        raise ValueError(f"n's pixels {_coef_spatial(n, 3, nl)} do not match the map's {tuple(spatial)}")
+    out = torch.empty((E,) + tuple(spatial) + ((3,) if rgb else ()), dtype=out_dtype, device=device)
+    return n.contiguous(), out
+
+
+def relight_hsh_specular(coef, n, lu, lv, basis="hsh16", *, kd=1.0, ks=0.0, exp=1, layout="pixel",
+                         normal_layout="pixel", out_dtype=torch.float32):
+    """Specular enhancement of fp32 HSH maps under a normal map on the GPU in one launch
+    (``rti_relight_hsh_specular``): per channel kd·L(lu, lv) + ks·max(0, n·H)^exp with L ``relight``'s float32
+    value and H the half vector between the light and the viewer; the highlight is white.  The maps and the normal
+    are read once for every direction.
+
+    coef: CUDA fp32; one map [H, W, k] / [P, k] or an RGB fit [3, H, W, k] / [3, P, k]; with layout="planar"
+    [k, H, W] / [k, P] and [3, k, H, W] / [3, k, P] (read as ``hsh_normals`` reads them).  n: fp32 normals of the
+    same pixels, [H, W, 3] (normal_layout="pixel") or [3, H, W]: ``hsh_normals(coef)``, optionally through
+    ``normals_unsharp``.  lu, lv: scalars or up to 16 directions (more raise ValueError).  Returns [E, H, W] or
+    [E, H, W, 3], without the leading E for scalar directions, in out_dtype: float32, or int32 / uint8 converted as
+    ``relight`` does.  NaN normals give NaN pixels.  PTM maps raise NotImplementedError: ``relight_rgb_enhanced``
+    renders those."""
+    b = _specular_basis(basis)
+    k = _HSH8_TERMS[b]
+    cl, nl = _layout_id(layout), _normal_layout_id(normal_layout)
+    luv, scalar = _specular_dirs(lu, lv)
+    _require_cuda(coef, "coef")
+    if coef.dtype != torch.float32:
+        raise ValueError(f"coef must be float32; got {coef.dtype}")
+    if cl == L.RTI_COEF_PIXEL_MAJOR:
+        rgb = coef.dim() == 4 or (coef.dim() == 3 and coef.shape[0] == 3)
+    else:
+        rgb = coef.dim() == 4 or (coef.dim() == 3 and coef.shape[0] == 3 and coef.shape[1] == k)
+    if coef.dim() < 2 or coef.dim() > 4:
+        raise ValueError(f"coef must be one HSH map or three, [3, ...]; got {tuple(coef.shape)}")
+    spatial = _rgb_spatial(coef, k, cl) if rgb else _coef_spatial(coef, k, cl)
+    nc, out = _specular_frame(n, nl, spatial, luv.shape[0], rgb, out_dtype, coef.device)
+    relight_hsh_specular_into(coef.contiguous(), nc, lu, lv, out, basis=b, kd=kd, ks=ks, exp=exp, layout=cl,
+                              normal_layout=nl)
+    return out[0] if scalar else out
+
+
+def relight_hsh8_specular(q, n, lu, lv, *, kd=1.0, ks=0.0, exp=1, normal_layout="pixel", out_dtype=torch.float32):
+    """Specular enhancement of a quantised RGB HSH map under a normal map on the GPU in one launch, from the bytes
+    (``rti_relight_hsh8_specular``): ``relight_hsh_specular(dequantise_hsh(q), n, ...)`` bit for bit, without the
+    fp32 maps.  The loaded-file workflow: ``q = read_rti(path, quantised=True)[1].to("cuda")``,
+    ``n = normals_unsharp(hsh8_normals(q), ...)`` once, then one launch per frame.
+
+    q: a ``QuantisedHSH`` on the GPU; the rest as ``relight_hsh_specular``.  Returns [E, H, W, 3], without the
+    leading E for scalar directions."""
+    nl = _normal_layout_id(normal_layout)
+    luv, scalar = _specular_dirs(lu, lv)
+    _quantised(q, QuantisedHSH)
+    nc, out = _specular_frame(n, nl, q.shape, luv.shape[0], True, out_dtype, q.device)
+    relight_hsh8_specular_into(q.coef, q.qparams, nc, lu, lv, out, basis=q._basis, kd=kd, ks=ks, exp=exp,
+                               normal_layout=nl)
+    return out[0] if scalar else out
+
+
 # ---- light operators (RBF, fused PTM/HSH fit + evaluation) ----------------------------------
 
 def _query(qu, qv):

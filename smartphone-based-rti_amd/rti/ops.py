@@ -3,7 +3,8 @@
 ``relight_enhanced`` / ``map_unsharp`` / ``shade_normals`` / ``lrgb_from_rgb`` / ``relight_lrgb`` /
 ``lrgb_quantise`` / ``relight_lrgb8`` / ``hsh_quantise`` / ``relight_hsh8`` / ``hsh_normals`` / ``hsh8_normals`` /
 ``rgb8_quantise`` / ``relight_rgb8`` / ``rgb8_normals`` / ``relight_lrgb_enhanced`` / ``relight_lrgb8_enhanced`` /
-``relight_rgb8_enhanced`` / ``relight_rgb`` / ``relight_rgb_enhanced`` / ``rgb_normals``.
+``relight_rgb8_enhanced`` / ``relight_rgb`` / ``relight_rgb_enhanced`` / ``rgb_normals`` / ``relight_hsh_specular`` /
+``relight_hsh8_specular``.
 
 They let the fit and relight kernels sit inside torch programs (and
 ``torch.library`` fake-tensor tracing) while the compute stays in librti's
@@ -723,3 +724,72 @@ def rgb_normals(coef: torch.Tensor, planar: bool = False, normals_planar: bool =
 @rgb_normals.register_fake
 def _(coef, planar=False, normals_planar=False, weights=None):
     return _normal_triple(coef, coef.shape[2 if planar else 1], normals_planar)
+
+
+# ---- specular enhancement of HSH maps under a normal map --------------------
+
+def _specular_luv(luv):
+    """luv [E, 2] on any device -> (lu, lv) on the host: the directions travel as kernel arguments."""
+    if luv.dim() != 2 or luv.shape[1] != 2:
+        raise ValueError(f"luv must be [E, 2]; got {tuple(luv.shape)}")
+    h = luv.detach().cpu().double().numpy()
+    return h[:, 0], h[:, 1]
+
+
+def _specular_n(n, P, normals_planar):
+    api._require_cuda(n, "n")
+    if tuple(n.shape) != ((3, P) if normals_planar else (P, 3)):
+        raise ValueError(f"n must be {f'[3, {P}]' if normals_planar else f'[{P}, 3]'}; got {tuple(n.shape)}")
+    return n.contiguous()
+
+
+@torch.library.custom_op("rti::relight_hsh_specular", mutates_args=())
+def relight_hsh_specular(coef: torch.Tensor, n: torch.Tensor, luv: torch.Tensor, k: int = 16, kd: float = 1.0,
+                         ks: float = 0.0, exp: int = 1, planar: bool = False, normals_planar: bool = False,
+                         out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Specular enhancement of fp32 HSH maps under a normal map (``rti_relight_hsh_specular``).  coef CUDA fp32
+    [P, k] or [3, P, k] (or [k, P] / [3, k, P] if planar), k = 9 or 16, n fp32 [P, 3] (or [3, P] if normals_planar),
+    luv [E, 2] with E <= 16 (read on the host) -> [E, P] or [E, P, 3] in out_dtype (float32, int32 or uint8)."""
+    api._require_cuda(coef, "coef")
+    P = _hsh_map_pixels(coef, k, planar)
+    _same_device(coef=coef, n=n)
+    if out_dtype not in api._ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    lu, lv = _specular_luv(luv)
+    out = coef.new_empty((luv.shape[0], P) + ((3,) if coef.dim() == 3 else ()), dtype=out_dtype)
+    return api.relight_hsh_specular_into(coef.contiguous(), _specular_n(n, P, normals_planar), lu, lv, out,
+                                         basis=f"hsh{k}", kd=kd, ks=ks, exp=exp,
+                                         layout="planar" if planar else "pixel",
+                                         normal_layout="planar" if normals_planar else "pixel")
+
+
+@relight_hsh_specular.register_fake
+def _(coef, n, luv, k=16, kd=1.0, ks=0.0, exp=1, planar=False, normals_planar=False, out_dtype=torch.float32):
+    P = coef.shape[-1 if planar else -2]
+    return coef.new_empty((luv.shape[0], P) + ((3,) if coef.dim() == 3 else ()), dtype=out_dtype)
+
+
+@torch.library.custom_op("rti::relight_hsh8_specular", mutates_args=())
+def relight_hsh8_specular(coef8: torch.Tensor, qparams: torch.Tensor, n: torch.Tensor, luv: torch.Tensor,
+                          kd: float = 1.0, ks: float = 0.0, exp: int = 1, normals_planar: bool = False,
+                          out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Specular enhancement of a quantised RGB HSH map under a normal map (``rti_relight_hsh8_specular``).  coef8
+    CUDA uint8 [P, 3, k] with k = 9 or 16, qparams fp32 [2k], n and luv as ``relight_hsh_specular`` -> [E, P, 3]
+    in out_dtype (float32, int32 or uint8)."""
+    api._require_cuda(coef8, "coef8")
+    if coef8.dim() != 3 or coef8.shape[1] != 3 or coef8.shape[2] not in (9, 16):
+        raise ValueError(f"coef8 must be [P, 3, 9] or [P, 3, 16]; got {tuple(coef8.shape)}")
+    _same_device(coef8=coef8, n=n)
+    if out_dtype not in api._ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    P = coef8.shape[0]
+    lu, lv = _specular_luv(luv)
+    out = coef8.new_empty((luv.shape[0], P, 3), dtype=out_dtype)
+    return api.relight_hsh8_specular_into(coef8.contiguous(), qparams.contiguous(), _specular_n(n, P, normals_planar),
+                                          lu, lv, out, basis=f"hsh{coef8.shape[2]}", kd=kd, ks=ks, exp=exp,
+                                          normal_layout="planar" if normals_planar else "pixel")
+
+
+@relight_hsh8_specular.register_fake
+def _(coef8, qparams, n, luv, kd=1.0, ks=0.0, exp=1, normals_planar=False, out_dtype=torch.float32):
+    return coef8.new_empty((luv.shape[0], coef8.shape[0], 3), dtype=out_dtype)
