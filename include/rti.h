@@ -948,8 +948,8 @@ int rti_relight_rgb8_enhanced(const uint8_t* coef8, int64_t P, const double* qpa
  * through LDS if coef is 16-byte aligned with a channel stride that is a multiple of 4, and stores its 192 output
  * elements as whole dwords if out is 4-byte aligned (U8: and P % 4 == 0); anything else loads and stores per lane,
  * with the same bits.  The basis rows of up to 64 directions at a time are kept in LDS.
- * Not built: fp64 RGB maps, planar RGB output, diffuse gain for HSH, a multi-GPU wrapper.  (Several directions per
- * launch of an enhanced rendering: rti_relight_hsh_specular, below, for HSH maps.) */
+ * Not built: fp64 RGB maps, planar RGB output, a multi-GPU wrapper.  (Several directions per launch of an enhanced
+ * rendering, and diffuse gain for HSH maps: rti_relight_hsh_specular and rti_relight_hsh_gain, below.) */
 int rti_relight_rgb(const float* coef, int basis, int coef_layout, int64_t coef_channel_stride, int64_t P,
                     const double* luv, int E, void* out, int out_dtype, rti_stream_t stream);
 int rti_relight_rgb_enhanced(const float* coef, int coef_layout, int64_t coef_channel_stride, int64_t P,
@@ -1005,7 +1005,7 @@ int rti_rgb_normals(const float* coef, int coef_layout, int64_t coef_channel_str
  *   out:                         4-byte aligned, and for U8 also P % 4 == 0.
  * Anything else, and the last partial wave of any launch, loads and stores per lane through the same per-pixel
  * function and gives the same bits.
- * Not built: diffuse gain for HSH, planar RGB output, a multi-GPU wrapper. */
+ * Not built: planar RGB output, a multi-GPU wrapper.  (Diffuse gain for HSH maps: rti_relight_hsh_gain, below.) */
 #define RTI_SPECULAR_MAX_DIRS 16
 int rti_relight_hsh_specular(const float* coef, int basis, int coef_layout, int C, int64_t coef_channel_stride,
                              int64_t P, const float* normals, int normal_layout,
@@ -1015,6 +1015,56 @@ int rti_relight_hsh8_specular(const uint8_t* coef8, int basis, int64_t P, const 
                               const float* normals, int normal_layout,
                               double kd, double ks, int spec_exp, const double* luv /* HOST [E][2] */, int E,
                               void* out, int out_dtype, rti_stream_t stream);
+
+/* ---- device: diffuse gain for HSH maps under a normal map (rti_hsh_gain.hip) ------------------------
+ * The diffuse-gain mode of rti_relight_enhanced for the bases without a closed-form peak.  For a PTM whose gradient
+ * vanishes at its peak l0, Malzbender's transform of the six coefficients is, identically,
+ *   L'(l) = L(l) + (g − 1)·(L(l) − L(l0)):
+ * it keeps the peak's value and direction and multiplies the fall-off away from the peak by g.  The expression names
+ * no curvature, so it carries over to any basis once a peak direction is known; for an HSH map that is the normal map
+ * rti_hsh_normals / rti_hsh8_normals produce once per object (optionally sharpened by rti_map_unsharp), which these
+ * entries read as rti_relight_hsh_specular does; the semantics are build-defined.  Per pixel p, channel c and
+ * direction e, every operation rounded, each expression left to right as written, nothing contracted except the fmaf
+ * chain named:
+ *   V_c = rti_relight's F32 value of channel c's coefficients at (lu_e, lv_e), bit for bit (as rti_relight_hsh_specular
+ *         states it; for the 8-bit map c_j = (float)raw_j·step_j + bias_j as rti_relight_hsh8 states it)
+ *   A_c = the same F32 value at the pixel's own direction (n_x, n_y), the fp32 normal components as they are:
+ *         basis_eval<float>(n_x, n_y), acc = c_0·b_0, acc = fmaf(c_j, b_j, acc) for j = 1..k−1.  That is
+ *         rti_relight(coef_c, (double)n_x, (double)n_y) at that pixel, bit for bit.
+ *   d   = (double)V_c − (double)A_c
+ *   v_c = (double)V_c + gm1·d            fp64, no contraction; gm1 = gain − 1 formed on the HOST in fp64
+ *   out = NaN if n_x, n_y or n_z is NaN, else v_c; converted once (F32; I32 / U8 as rti_relight)
+ * The normal is not checked for unit length and n_z is read only for the NaN test (the basis clamps a direction
+ * outside the unit disc as it does a light's).  A non-finite coefficient propagates through V and A as the arithmetic
+ * gives.  gain is any finite double; zero and negative values are allowed.  Hence: gain = 1 under finite normals and
+ * finite coefficients is the plain relight exactly (gm1 = 0); gain = 0 gives A_c for every direction (to fp64
+ * rounding); a light direction equal to a pixel's (n_x, n_y) gives A_c at that pixel for every gain.
+ * rti_relight_hsh_gain: coef, basis, coef_layout, C, coef_channel_stride, P, normals, normal_layout, luv, E, out and
+ *   out_dtype exactly as rti_relight_hsh_specular takes them: C = 1 or 3 maps, out[e][p] or out[e][p][c], luv [E][2]
+ *   fp64 on the HOST with 1 <= E <= RTI_SPECULAR_MAX_DIRS (the directions travel as one kernel argument, 16 × 16
+ *   bytes).  4·C·k + 12 bytes in and C·sizeof(out) per direction out per pixel.
+ * rti_relight_hsh8_gain: coef8 / qparams as rti_relight_hsh8 takes them, the rest as above; out[e][p][c].  The image
+ *   equals rti_relight_hsh_gain's of the dequantised maps bit for bit.  3k + 12 bytes in and 3·sizeof(out) per
+ *   direction out per pixel.
+ * Both: one launch, no allocation, no copy, no synchronisation, capturable in a hipGraph (the directions and the gain
+ *   are then part of the capture).  The coefficients or bytes and the normal are read once for all E directions; the
+ *   basis at the normal (three fp32 square roots and two divisions) and the C anchors are formed once per pixel and
+ *   launch, not per direction.
+ * Every argument check answers before any HIP call.  RTI_ERR_BAD_ARG: the cases of rti_relight_hsh_specular (a null
+ * pointer; P < 1; E outside [1, RTI_SPECULAR_MAX_DIRS]; C other than 1 or 3; a channel stride below dense (C = 3); a
+ * bad coefficient or normal layout; a non-finite luv value; qparams off 4 bytes) and a non-finite gain.
+ * RTI_ERR_UNSUPPORTED: a basis other than HSH-9 / HSH-16 (PTM-6 has rti_relight_enhanced and its RGB forms); an
+ * out_dtype other than F32 / I32 / U8.
+ * Lane map, fast paths and their alignment rules: rti_relight_hsh_specular's, above.  Anything they cannot serve, and
+ * the last partial wave of any launch, loads and stores per lane through the same per-pixel functions and gives the
+ * same bits.
+ * Not built: planar RGB output, a gain combined with a highlight, fp64 maps, a multi-GPU wrapper. */
+int rti_relight_hsh_gain(const float* coef, int basis, int coef_layout, int C, int64_t coef_channel_stride,
+                         int64_t P, const float* normals, int normal_layout, double gain,
+                         const double* luv /* HOST [E][2] */, int E, void* out, int out_dtype, rti_stream_t stream);
+int rti_relight_hsh8_gain(const uint8_t* coef8, int basis, int64_t P, const float* qparams,
+                          const float* normals, int normal_layout, double gain,
+                          const double* luv /* HOST [E][2] */, int E, void* out, int out_dtype, rti_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,22 +1,20 @@
-// rti_hsh_specular.hip -- specular enhancement of HSH maps under a normal map (gfx950).
+// rti_hsh_gain.hip -- diffuse gain for HSH maps under a normal map (gfx950).
 //
-//     rti_relight_hsh_specular    one or three fp32 HSH maps + a normal map -> E images
-//     rti_relight_hsh8_specular   the bytes of an .rti file + a normal map  -> E interleaved RGB images
+//     rti_relight_hsh_gain    one or three fp32 HSH maps + a normal map -> E images
+//     rti_relight_hsh8_gain   the bytes of an .rti file + a normal map  -> E interleaved RGB images
 //
-// An HSH map has no closed-form peak (rti_hsh_normals searches for it, once per object), so these entries read a
-// normal map instead of recomputing the normal per frame as rti_relight_enhanced does.  Per pixel, channel and
-// direction the value is include/rti.h's: V = rti_relight's F32 value (hsh_px::dot_k of the basis row that
-// hsh_eval<float> forms), S = ks·powi(max(0, n·H), spec_exp) in fp64, kd·V + S in fp64 without contraction,
-// converted once.  The half vectors are formed on the host (light_frame) and travel with the directions as one
-// kernel argument, so a call copies and allocates nothing.
+// Diffuse gain keeps a pixel's value at its peak direction and multiplies the fall-off away from it by g:
+// L'(l) = L(l) + (g − 1)·(L(l) − L(l0)).  For a PTM that is Malzbender's transform of the six coefficients; in this
+// form it names no curvature, so it holds for any basis once the peak direction l0 is known, and for an HSH map that
+// is the normal map these entries read (rti_hsh_normals, once per object), as rti_relight_hsh_specular does.  Per
+// pixel and channel the value is include/rti.h's: V = rti_relight's F32 value at the light, A = the same F32 value at
+// the pixel's own (n_x, n_y) -- hsh_eval<float> at a per-pixel direction, once per pixel and launch -- and
+// V + gm1·(V − A) in fp64 without contraction, converted once.
 //
-// Lane map: rti_hsh8.hip's.  One pixel per lane, a wave owns 64 consecutive pixels, a workgroup 256.  A full wave
-// moves its contiguous run of bytes, of a pixel-major channel's rows and of pixel-major normals (64 x 12 B) as
-// whole 16-byte pieces through its LDS slab, and its output elements leave through the slab as whole dwords.
-// Planar maps and normals are read per lane, coalesced as they are.  Anything the pieces cannot serve (a pointer
-// off its alignment, uint8 output with P % 4 != 0, the last partial wave) loads and stores per lane; every path
-// runs specular_value, so the bits do not depend on it.  The coefficients or bytes and the normal are read once
-// for all E directions; the E basis rows are formed once per workgroup in LDS.
+// Lane map, staging and output rows: rti_hsh_specular.hip's (rti_hsh_render_px.h).  One pixel per lane; the
+// coefficients or bytes and the normal are read once for all E directions, the C anchors are formed once, the E basis
+// rows of the lights once per workgroup in LDS.  Every path runs anchors and gain_value, so the bits do not depend
+// on it.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -25,7 +23,6 @@
 #include "rti_basis.h"
 #include "rti_convert.h"
 #include "rti_hsh_render_px.h"
-#include "rti_shade.h"
 #include "rti_stack.h"
 
 namespace rti {
@@ -33,35 +30,48 @@ namespace {
 
 using namespace hsh_render;  // the chain, the slab runs, the basis rows, the normal and the output rows
 
-// a direction and its half vector, formed on the host in fp64 (light_frame)
 struct Dir {
   double lu, lv;
-  double hx, hy, hz;
 };
 struct Dirs {
   Dir d[MAXE];
 };
-struct Spec {
-  double kd, ks;
-  int e;
-};
 
-// ---- the per-pixel function ------------------------------------------------------------------------------------
-// C channels of one pixel at one direction: b its basis row, n the pixel's normal.  The highlight is white: one S
-// for the C channels.  A NaN normal component gives NaN whatever ks is.
+// ---- the per-pixel functions -------------------------------------------------------------------------------------
+// A_c: rti_relight's F32 value of each channel at the pixel's own direction (n_x, n_y), the fp32 components as they
+// are (hsh_eval clamps outside the disc).  Three square roots and two divisions per pixel and launch.
+template <int K, int C>
+__device__ __forceinline__ void anchors(const float (&c)[C][K], const float (&n)[3], float (&A)[C]) {
+  float b[K];
+  hsh_eval<float>(n[0], n[1], K, b);  // basis_eval<float>'s HSH branch
+#pragma unroll
+  for (int ch = 0; ch < C; ++ch) A[ch] = dot_k<K>(c[ch], b);
+}
+
+// C channels of one pixel at one direction: b the light's basis row.  A NaN normal component gives NaN.
 template <int K, int C, typename TO>
-__device__ __forceinline__ void specular_value(const float (&c)[C][K], const float* __restrict__ b,
-                                               const float (&n)[3], const Dir& d, const Spec& q, TO (&o)[C]) {
+__device__ __forceinline__ void gain_value(const float (&c)[C][K], const float* __restrict__ b, const float (&A)[C],
+                                           bool bad, double gm1, TO (&o)[C]) {
 #pragma clang fp contract(off)
-  const double nx = (double)n[0], ny = (double)n[1], nz = (double)n[2];
-  const double h = nx * d.hx + ny * d.hy + nz * d.hz;
-  const double S = q.ks * powi(h > 0.0 ? h : 0.0, q.e);
-  const bool bad = nx != nx || ny != ny || nz != nz;
 #pragma unroll
   for (int ch = 0; ch < C; ++ch) {
-    const double v = q.kd * (double)dot_k<K>(c[ch], b) + S;
+    const double V = (double)dot_k<K>(c[ch], b);
+    const double d = V - (double)A[ch];
+    const double v = V + gm1 * d;
     o[ch] = cvt_out<TO>(bad ? (double)NAN : v);
   }
+}
+
+// the anchors, then the wave's 64 pixels at every direction
+template <int K, int C, typename TO>
+__device__ __forceinline__ void render_gain(const float (&c)[C][K], const float (&n)[3], const float* __restrict__ btab,
+                                            int E, double gm1, int64_t P, int64_t wave_px, int lane, bool live,
+                                            bool vout, u32x4* __restrict__ slab, TO* __restrict__ out) {
+  float A[C];
+  anchors<K, C>(c, n, A);
+  const bool bad = n[0] != n[0] || n[1] != n[1] || n[2] != n[2];
+  render<C, TO>(E, P, wave_px, lane, live, vout, slab, out,
+                [&](int e, TO (&o)[C]) { gain_value<K, C, TO>(c, btab + e * K, A, bad, gm1, o); });
 }
 
 // ---- kernels ------------------------------------------------------------------------------------------------------
@@ -70,9 +80,9 @@ __device__ __forceinline__ void specular_value(const float (&c)[C][K], const flo
 
 template <int K, typename TO>
 __global__ void __launch_bounds__(256)
-relight_hsh8_specular_k(const uint8_t* __restrict__ coef8, int64_t P, int vin, const float* __restrict__ qparams,
-                        const float* __restrict__ normals, int nl, int vn, int vout, Spec q, Dirs dirs, int E,
-                        TO* __restrict__ out) {
+relight_hsh8_gain_k(const uint8_t* __restrict__ coef8, int64_t P, int vin, const float* __restrict__ qparams,
+                    const float* __restrict__ normals, int nl, int vn, int vout, double gm1, Dirs dirs, int E,
+                    TO* __restrict__ out) {
   constexpr int NB = 3 * K, NW = (NB + 3) / 4;
   constexpr int SLAB = render_slab(run_v4<NB>());
   __shared__ u32x4 slabs[4 * SLAB];
@@ -101,15 +111,13 @@ relight_hsh8_specular_k(const uint8_t* __restrict__ coef8, int64_t P, int vin, c
   dequantise_px<K>(w, qs, c);
   float n[3];
   load_normal(normals, nl, vn && full, P, wave_px, lane, live, slab, n);
-  render<3, TO>(E, P, wave_px, lane, live, vout && full, slab, out,
-                [&](int e, TO (&o)[3]) { specular_value<K, 3, TO>(c, btab + e * K, n, dirs.d[e], q, o); });
+  render_gain<K, 3, TO>(c, n, btab, E, gm1, P, wave_px, lane, live, vout && full, slab, out);
 }
 
 template <int K, int C, int CL, typename TO>
 __global__ void __launch_bounds__(256)
-relight_hsh_specular_k(const float* __restrict__ coef, int64_t cs, int64_t P, int vin,
-                       const float* __restrict__ normals, int nl, int vn, int vout, Spec q, Dirs dirs, int E,
-                       TO* __restrict__ out) {
+relight_hsh_gain_k(const float* __restrict__ coef, int64_t cs, int64_t P, int vin, const float* __restrict__ normals,
+                   int nl, int vn, int vout, double gm1, Dirs dirs, int E, TO* __restrict__ out) {
   constexpr int SLAB = render_slab(CL == RTI_COEF_PIXEL_MAJOR ? run_v4<4 * K>() : 0);
   __shared__ u32x4 slabs[4 * SLAB];
   __shared__ float btab[MAXE * K];
@@ -139,8 +147,7 @@ relight_hsh_specular_k(const float* __restrict__ coef, int64_t cs, int64_t P, in
   }
   float n[3];
   load_normal(normals, nl, vn && full, P, wave_px, lane, live, slab, n);
-  render<C, TO>(E, P, wave_px, lane, live, vout && full, slab, out,
-               [&](int e, TO (&o)[C]) { specular_value<K, C, TO>(c, btab + e * K, n, dirs.d[e], q, o); });
+  render_gain<K, C, TO>(c, n, btab, E, gm1, P, wave_px, lane, live, vout && full, slab, out);
 }
 
 // ---- launchers and checks -----------------------------------------------------------------------------------------
@@ -150,7 +157,7 @@ struct Frame {
   int64_t P;
   const float* normals;
   int nl, vn, vout;
-  Spec q;
+  double gm1;
   Dirs dirs;
   int E;
   void* out;
@@ -161,8 +168,8 @@ template <int K>
 void launch8(const uint8_t* coef8, int vin, const float* qparams, const Frame& a, int out_dtype) {
   with_out(out_dtype, [&](auto t) {
     using TO = decltype(t);
-    hipLaunchKernelGGL((relight_hsh8_specular_k<K, TO>), dim3(grid_1d(a.P, CHUNK)), dim3(256), 0, a.s, coef8, a.P, vin,
-                       qparams, a.normals, a.nl, a.vn, a.vout, a.q, a.dirs, a.E, static_cast<TO*>(a.out));
+    hipLaunchKernelGGL((relight_hsh8_gain_k<K, TO>), dim3(grid_1d(a.P, CHUNK)), dim3(256), 0, a.s, coef8, a.P, vin,
+                       qparams, a.normals, a.nl, a.vn, a.vout, a.gm1, a.dirs, a.E, static_cast<TO*>(a.out));
   });
 }
 
@@ -170,8 +177,8 @@ template <int K, int C, int CL>
 void launch_t(const float* coef, int64_t cs, int vin, const Frame& a, int out_dtype) {
   with_out(out_dtype, [&](auto t) {
     using TO = decltype(t);
-    hipLaunchKernelGGL((relight_hsh_specular_k<K, C, CL, TO>), dim3(grid_1d(a.P, CHUNK)), dim3(256), 0, a.s, coef, cs,
-                       a.P, vin, a.normals, a.nl, a.vn, a.vout, a.q, a.dirs, a.E, static_cast<TO*>(a.out));
+    hipLaunchKernelGGL((relight_hsh_gain_k<K, C, CL, TO>), dim3(grid_1d(a.P, CHUNK)), dim3(256), 0, a.s, coef, cs, a.P,
+                       vin, a.normals, a.nl, a.vn, a.vout, a.gm1, a.dirs, a.E, static_cast<TO*>(a.out));
   });
 }
 
@@ -193,13 +200,11 @@ void launch_c(const float* coef, int C, int layout, int64_t cs, int vin, const F
 
 // the checks the two entries share after their coefficients, in the order include/rti.h lists the arguments (E
 // before the values of luv it counts); fills everything of `a` but the stream
-int check_frame(const char* entry, int64_t P, const float* normals, int normal_layout, double kd, double ks,
-                int spec_exp, const double* luv, int E, void* out, int out_dtype, Frame& a) {
+int check_frame(const char* entry, int64_t P, const float* normals, int normal_layout, double gain, const double* luv,
+                int E, void* out, int out_dtype, Frame& a) {
   if (normal_layout != RTI_NORMAL_PIXEL_MAJOR && normal_layout != RTI_NORMAL_PLANAR)
     return fail(RTI_ERR_BAD_ARG, "%s: normal layout %d", entry, normal_layout);
-  if (!std::isfinite(kd) || !std::isfinite(ks)) return fail(RTI_ERR_BAD_ARG, "%s: non-finite kd or ks", entry);
-  if (spec_exp < 1 || spec_exp > 255)
-    return fail(RTI_ERR_BAD_ARG, "%s: spec_exp %d outside [1, 255]", entry, spec_exp);
+  if (!std::isfinite(gain)) return fail(RTI_ERR_BAD_ARG, "%s: non-finite gain", entry);
   if (E < 1 || E > MAXE) return fail(RTI_ERR_BAD_ARG, "%s: E = %d outside [1, %d]", entry, E, MAXE);
   for (int i = 0; i < 2 * E; ++i)
     if (!std::isfinite(luv[i])) return fail(RTI_ERR_BAD_ARG, "%s: non-finite light direction", entry);
@@ -210,11 +215,8 @@ int check_frame(const char* entry, int64_t P, const float* normals, int normal_l
   a.nl = normal_layout;
   a.vn = normals_staged(normals, normal_layout);
   a.vout = rows_as_dwords(out, out_dtype, P);
-  a.q = Spec{kd, ks, spec_exp};
-  for (int i = 0; i < E; ++i) {
-    const LightFrame f = light_frame(luv[2 * i], luv[2 * i + 1]);
-    a.dirs.d[i] = Dir{f.lu, f.lv, f.hx, f.hy, f.hz};
-  }
+  a.gm1 = gain - 1.0;
+  for (int i = 0; i < E; ++i) a.dirs.d[i] = Dir{luv[2 * i], luv[2 * i + 1]};
   a.E = E;
   a.out = out;
   return RTI_OK;
@@ -225,11 +227,10 @@ int check_frame(const char* entry, int64_t P, const float* normals, int normal_l
 
 using namespace rti;
 
-extern "C" int rti_relight_hsh_specular(const float* coef, int basis, int coef_layout, int C,
-                                        int64_t coef_channel_stride, int64_t P, const float* normals,
-                                        int normal_layout, double kd, double ks, int spec_exp, const double* luv,
-                                        int E_, void* out, int out_dtype, rti_stream_t stream) {
-  const char* const E = "rti_relight_hsh_specular";
+extern "C" int rti_relight_hsh_gain(const float* coef, int basis, int coef_layout, int C, int64_t coef_channel_stride,
+                                    int64_t P, const float* normals, int normal_layout, double gain, const double* luv,
+                                    int E_, void* out, int out_dtype, rti_stream_t stream) {
+  const char* const E = "rti_relight_hsh_gain";
   if (int st = check_pointers(E, {coef, normals, luv, out})) return st;
   if (!hsh_basis(basis))
     return fail(RTI_ERR_UNSUPPORTED, "%s: basis %d (HSH-9 and HSH-16 only; PTM-6 has rti_relight_rgb_enhanced)", E, basis);
@@ -239,7 +240,7 @@ extern "C" int rti_relight_hsh_specular(const float* coef, int basis, int coef_l
   const int k = basis_terms(basis);
   if (int st = check_coef_stride(E, coef_view(coef, coef_layout, k, P, coef_channel_stride), P, C)) return st;
   Frame a{};  // directions past E stay zero
-  if (int st = check_frame(E, P, normals, normal_layout, kd, ks, spec_exp, luv, E_, out, out_dtype, a)) return st;
+  if (int st = check_frame(E, P, normals, normal_layout, gain, luv, E_, out, out_dtype, a)) return st;
   a.s = (hipStream_t)stream;
   const int64_t cs = coef_channel_stride ? coef_channel_stride : P * k;
   const int vin = maps_staged(coef, coef_layout, C, cs);
@@ -251,18 +252,17 @@ extern "C" int rti_relight_hsh_specular(const float* coef, int basis, int coef_l
   return check_launch(E);
 }
 
-extern "C" int rti_relight_hsh8_specular(const uint8_t* coef8, int basis, int64_t P, const float* qparams,
-                                         const float* normals, int normal_layout, double kd, double ks,
-                                         int spec_exp, const double* luv, int E_, void* out, int out_dtype,
-                                         rti_stream_t stream) {
-  const char* const E = "rti_relight_hsh8_specular";
+extern "C" int rti_relight_hsh8_gain(const uint8_t* coef8, int basis, int64_t P, const float* qparams,
+                                     const float* normals, int normal_layout, double gain, const double* luv, int E_,
+                                     void* out, int out_dtype, rti_stream_t stream) {
+  const char* const E = "rti_relight_hsh8_gain";
   if (int st = check_pointers(E, {coef8, qparams, normals, luv, out})) return st;
   if (!hsh_basis(basis))
     return fail(RTI_ERR_UNSUPPORTED, "%s: basis %d (HSH-9 and HSH-16 only; PTM-6 has rti_relight_rgb8_enhanced)", E, basis);
   if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", E);
   if (!aligned_to(qparams, 4)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 4-byte aligned", E);
   Frame a{};  // directions past E stay zero
-  if (int st = check_frame(E, P, normals, normal_layout, kd, ks, spec_exp, luv, E_, out, out_dtype, a)) return st;
+  if (int st = check_frame(E, P, normals, normal_layout, gain, luv, E_, out, out_dtype, a)) return st;
   a.s = (hipStream_t)stream;
   const int vin = aligned_to(coef8, 16) ? 1 : 0;
   note_launches(1);

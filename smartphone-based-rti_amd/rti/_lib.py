@@ -40,7 +40,7 @@ RTI_NORMAL_PLANAR = 1  # normals[3][p]
 RTI_ENHANCE_DIFFUSE_GAIN = 1  # rti_relight_enhanced modes
 RTI_ENHANCE_SPECULAR = 2
 RTI_UNSHARP_MAX_RADIUS = 32  # rti_map_unsharp: the largest Gaussian radius
-RTI_SPECULAR_MAX_DIRS = 16  # rti_relight_hsh_specular: the most directions of a launch
+RTI_SPECULAR_MAX_DIRS = 16  # rti_relight_hsh_specular, rti_relight_hsh_gain: the most directions of a launch
 
 RTI_KERNEL_AUTO = 0
 RTI_KERNEL_VALU = 1
@@ -204,6 +204,10 @@ SIGNATURES = {
                                           _c_void_p]),
     "rti_relight_hsh8_specular": (_c_int, [_c_void_p, _c_int, _c_i64, _c_void_p, _c_void_p, _c_int, _c_double,
                                            _c_double, _c_int, _c_double_p, _c_int, _c_void_p, _c_int, _c_void_p]),
+    "rti_relight_hsh_gain": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_i64, _c_i64, _c_void_p, _c_int, _c_double,
+                                      _c_double_p, _c_int, _c_void_p, _c_int, _c_void_p]),
+    "rti_relight_hsh8_gain": (_c_int, [_c_void_p, _c_int, _c_i64, _c_void_p, _c_void_p, _c_int, _c_double,
+                                       _c_double_p, _c_int, _c_void_p, _c_int, _c_void_p]),
 }
 
 _lock = threading.Lock()

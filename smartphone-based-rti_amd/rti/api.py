@@ -2315,11 +2315,11 @@ def rgb_normals(coef, *, layout="pixel", normal_layout="pixel", weights=None, re
 
 # ---- specular enhancement of HSH maps under a normal map (rti_hsh_specular.hip) -
 
-def _specular_basis(basis):
+def _specular_basis(basis, what="relight_hsh_specular"):
     """A basis name or id -> the id of HSH-9 or HSH-16; PTM-6 has entries of its own."""
     b = basis_id(basis)
     if b not in _HSH8_NAMES:
-        raise NotImplementedError(f"relight_hsh_specular reads HSH-9 and HSH-16 maps only; got basis {basis!r} "
+        raise NotImplementedError(f"{what} reads HSH-9 and HSH-16 maps only; got basis {basis!r} "
                                   "(PTM-6 maps: relight_rgb_enhanced, relight_enhanced)")
     return b
 
@@ -2397,6 +2397,20 @@ def relight_hsh8_specular_into(coef8, qparams, n, lu, lv, out, *, basis="hsh16",
     return out
 
 
+def _specular_maps(coef, k, cl):
+    """One CUDA fp32 HSH map or three of k terms in layout cl -> (spatial shape, whether there are three)."""
+    _require_cuda(coef, "coef")
+    if coef.dtype != torch.float32:
+        raise ValueError(f"coef must be float32; got {coef.dtype}")
+    if cl == L.RTI_COEF_PIXEL_MAJOR:
+        rgb = coef.dim() == 4 or (coef.dim() == 3 and coef.shape[0] == 3)
+    else:
+        rgb = coef.dim() == 4 or (coef.dim() == 3 and coef.shape[0] == 3 and coef.shape[1] == k)
+    if coef.dim() < 2 or coef.dim() > 4:
+        raise ValueError(f"coef must be one HSH map or three, [3, ...]; got {tuple(coef.shape)}")
+    return (_rgb_spatial(coef, k, cl) if rgb else _coef_spatial(coef, k, cl)), rgb
+
+
 def _specular_frame(n, nl, spatial, E, rgb, out_dtype, device):
     """What the two specular renderers do before their launch: n's pixels against the map's, and the output ->
     (n contiguous, out [E, *spatial(, 3)])."""
@@ -2426,19 +2440,9 @@ def relight_hsh_specular(coef, n, lu, lv, basis="hsh16", *, kd=1.0, ks=0.0, exp=
     ``relight`` does.  NaN normals give NaN pixels.  PTM maps raise NotImplementedError: ``relight_rgb_enhanced``
     renders those."""
     b = _specular_basis(basis)
-    k = _HSH8_TERMS[b]
     cl, nl = _layout_id(layout), _normal_layout_id(normal_layout)
     luv, scalar = _specular_dirs(lu, lv)
-    _require_cuda(coef, "coef")
-    if coef.dtype != torch.float32:
-        raise ValueError(f"coef must be float32; got {coef.dtype}")
-    if cl == L.RTI_COEF_PIXEL_MAJOR:
-        rgb = coef.dim() == 4 or (coef.dim() == 3 and coef.shape[0] == 3)
-    else:
-        rgb = coef.dim() == 4 or (coef.dim() == 3 and coef.shape[0] == 3 and coef.shape[1] == k)
-    if coef.dim() < 2 or coef.dim() > 4:
-        raise ValueError(f"coef must be one HSH map or three, [3, ...]; got {tuple(coef.shape)}")
-    spatial = _rgb_spatial(coef, k, cl) if rgb else _coef_spatial(coef, k, cl)
+    spatial, rgb = _specular_maps(coef, _HSH8_TERMS[b], cl)
     nc, out = _specular_frame(n, nl, spatial, luv.shape[0], rgb, out_dtype, coef.device)
     relight_hsh_specular_into(coef.contiguous(), nc, lu, lv, out, basis=b, kd=kd, ks=ks, exp=exp, layout=cl,
                               normal_layout=nl)
@@ -2459,6 +2463,92 @@ def relight_hsh8_specular(q, n, lu, lv, *, kd=1.0, ks=0.0, exp=1, normal_layout=
     nc, out = _specular_frame(n, nl, q.shape, luv.shape[0], True, out_dtype, q.device)
     relight_hsh8_specular_into(q.coef, q.qparams, nc, lu, lv, out, basis=q._basis, kd=kd, ks=ks, exp=exp,
                                normal_layout=nl)
+    return out[0] if scalar else out
+
+
+# ---- diffuse gain for HSH maps under a normal map (rti_hsh_gain.hip) ------------
+
+def _gain_value(gain):
+    g = float(gain)
+    if not np.isfinite(g):
+        raise ValueError(f"gain must be finite; got {gain!r}")
+    return g
+
+
+def relight_hsh_gain_into(coef, n, lu, lv, out, *, basis="hsh16", gain=1.0, layout="pixel", normal_layout="pixel"):
+    """Launch ``rti_relight_hsh_gain`` on preallocated tensors (no allocation, no copy, graph-capturable: the
+    directions and the gain travel as kernel arguments and become part of a capture).
+
+    coef, n, lu, lv and out exactly as ``relight_hsh_specular_into`` takes them; gain: any finite value."""
+    b = _specular_basis(basis, "relight_hsh_gain")
+    k = _HSH8_TERMS[b]
+    _require_cuda(coef, "coef")
+    P = _specular_normals(n, coef)
+    if coef.dtype != torch.float32 or not coef.is_contiguous() or coef.numel() not in (P * k, 3 * P * k):
+        raise ValueError(f"coef must be contiguous float32 with {k} or 3·{k} terms for each of n's {P} pixels; got "
+                         f"{coef.dtype} {tuple(coef.shape)}")
+    C = coef.numel() // (P * k)
+    luv, _ = _specular_dirs(lu, lv)
+    E = luv.shape[0]
+    odt = _out8_dtype(out)
+    st = L.lib().rti_relight_hsh_gain(_vp(coef), b, _layout_id(layout), C, 0, P, _vp(n),
+                                      _normal_layout_id(normal_layout), _gain_value(gain), _dptr(luv), E,
+                                      _map_out(out, "out", out.dtype, E * P * C, coef), odt, _stream_of(coef))
+    L.check(st, "rti_relight_hsh_gain")
+    return out
+
+
+def relight_hsh8_gain_into(coef8, qparams, n, lu, lv, out, *, basis="hsh16", gain=1.0, normal_layout="pixel"):
+    """Launch ``rti_relight_hsh8_gain`` on preallocated tensors (no allocation, no copy, graph-capturable).
+
+    coef8, qparams, n, lu, lv and out exactly as ``relight_hsh8_specular_into`` takes them; gain: any finite value."""
+    b = _specular_basis(basis, "relight_hsh8_gain")
+    k = _HSH8_TERMS[b]
+    P = _bytes_map(coef8, 3 * k, f"{3 * k} bytes")
+    if _specular_normals(n, coef8) != P:
+        raise ValueError(f"n has {n.numel() // 3} pixels, coef8 {P}")
+    luv, _ = _specular_dirs(lu, lv)
+    E = luv.shape[0]
+    odt = _out8_dtype(out)
+    st = L.lib().rti_relight_hsh8_gain(_vp(coef8), b, P, _qparams_arg(qparams, torch.float32, 2 * k, coef8), _vp(n),
+                                       _normal_layout_id(normal_layout), _gain_value(gain), _dptr(luv), E,
+                                       _map_out(out, "out", out.dtype, E * P * 3, coef8), odt, _stream_of(coef8))
+    L.check(st, "rti_relight_hsh8_gain")
+    return out
+
+
+def relight_hsh_gain(coef, n, lu, lv, basis="hsh16", *, gain=1.0, layout="pixel", normal_layout="pixel",
+                     out_dtype=torch.float32):
+    """Diffuse gain for fp32 HSH maps under a normal map on the GPU in one launch (``rti_relight_hsh_gain``): per
+    channel L(lu, lv) + (gain − 1)·(L(lu, lv) − L(n_x, n_y)) with L ``relight``'s float32 value.  The value at the
+    pixel's own normal and its direction stay, the fall-off away from it is multiplied by gain; gain = 1 is the plain
+    relight.  The maps and the normal are read once for every direction.
+
+    coef, n, lu, lv, layout, normal_layout and out_dtype as ``relight_hsh_specular`` takes them (n:
+    ``hsh_normals(coef)``, optionally through ``normals_unsharp``; up to 16 directions, more raise ValueError);
+    gain: any finite value.  Returns [E, H, W] or [E, H, W, 3], without the leading E for scalar directions.  NaN
+    normals give NaN pixels.  PTM maps raise NotImplementedError: ``relight_rgb_enhanced`` renders those."""
+    b = _specular_basis(basis, "relight_hsh_gain")
+    cl, nl = _layout_id(layout), _normal_layout_id(normal_layout)
+    luv, scalar = _specular_dirs(lu, lv)
+    spatial, rgb = _specular_maps(coef, _HSH8_TERMS[b], cl)
+    nc, out = _specular_frame(n, nl, spatial, luv.shape[0], rgb, out_dtype, coef.device)
+    relight_hsh_gain_into(coef.contiguous(), nc, lu, lv, out, basis=b, gain=gain, layout=cl, normal_layout=nl)
+    return out[0] if scalar else out
+
+
+def relight_hsh8_gain(q, n, lu, lv, *, gain=1.0, normal_layout="pixel", out_dtype=torch.float32):
+    """Diffuse gain for a quantised RGB HSH map under a normal map on the GPU in one launch, from the bytes
+    (``rti_relight_hsh8_gain``): ``relight_hsh_gain(dequantise_hsh(q), n, ...)`` bit for bit, without the fp32
+    maps.  The loaded-file workflow of ``relight_hsh8_specular``: the normals once per object, one launch per frame.
+
+    q: a ``QuantisedHSH`` on the GPU; the rest as ``relight_hsh_gain``.  Returns [E, H, W, 3], without the leading
+    E for scalar directions."""
+    nl = _normal_layout_id(normal_layout)
+    luv, scalar = _specular_dirs(lu, lv)
+    _quantised(q, QuantisedHSH)
+    nc, out = _specular_frame(n, nl, q.shape, luv.shape[0], True, out_dtype, q.device)
+    relight_hsh8_gain_into(q.coef, q.qparams, nc, lu, lv, out, basis=q._basis, gain=gain, normal_layout=nl)
     return out[0] if scalar else out
 
 

@@ -4,7 +4,7 @@
 ``lrgb_quantise`` / ``relight_lrgb8`` / ``hsh_quantise`` / ``relight_hsh8`` / ``hsh_normals`` / ``hsh8_normals`` /
 ``rgb8_quantise`` / ``relight_rgb8`` / ``rgb8_normals`` / ``relight_lrgb_enhanced`` / ``relight_lrgb8_enhanced`` /
 ``relight_rgb8_enhanced`` / ``relight_rgb`` / ``relight_rgb_enhanced`` / ``rgb_normals`` / ``relight_hsh_specular`` /
-``relight_hsh8_specular``.
+``relight_hsh8_specular`` / ``relight_hsh_gain`` / ``relight_hsh8_gain``.
 
 They let the fit and relight kernels sit inside torch programs (and
 ``torch.library`` fake-tensor tracing) while the compute stays in librti's
@@ -792,4 +792,55 @@ def relight_hsh8_specular(coef8: torch.Tensor, qparams: torch.Tensor, n: torch.T
 
 @relight_hsh8_specular.register_fake
 def _(coef8, qparams, n, luv, kd=1.0, ks=0.0, exp=1, normals_planar=False, out_dtype=torch.float32):
+    return coef8.new_empty((luv.shape[0], coef8.shape[0], 3), dtype=out_dtype)
+
+
+# ---- diffuse gain for HSH maps under a normal map ----------------------------
+
+@torch.library.custom_op("rti::relight_hsh_gain", mutates_args=())
+def relight_hsh_gain(coef: torch.Tensor, n: torch.Tensor, luv: torch.Tensor, k: int = 16, gain: float = 1.0,
+                     planar: bool = False, normals_planar: bool = False,
+                     out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Diffuse gain for fp32 HSH maps under a normal map (``rti_relight_hsh_gain``).  coef, n, luv, k, planar,
+    normals_planar and out_dtype as ``relight_hsh_specular`` -> [E, P] or [E, P, 3]."""
+    api._require_cuda(coef, "coef")
+    P = _hsh_map_pixels(coef, k, planar)
+    _same_device(coef=coef, n=n)
+    if out_dtype not in api._ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    lu, lv = _specular_luv(luv)
+    out = coef.new_empty((luv.shape[0], P) + ((3,) if coef.dim() == 3 else ()), dtype=out_dtype)
+    return api.relight_hsh_gain_into(coef.contiguous(), _specular_n(n, P, normals_planar), lu, lv, out,
+                                     basis=f"hsh{k}", gain=gain, layout="planar" if planar else "pixel",
+                                     normal_layout="planar" if normals_planar else "pixel")
+
+
+@relight_hsh_gain.register_fake
+def _(coef, n, luv, k=16, gain=1.0, planar=False, normals_planar=False, out_dtype=torch.float32):
+    P = coef.shape[-1 if planar else -2]
+    return coef.new_empty((luv.shape[0], P) + ((3,) if coef.dim() == 3 else ()), dtype=out_dtype)
+
+
+@torch.library.custom_op("rti::relight_hsh8_gain", mutates_args=())
+def relight_hsh8_gain(coef8: torch.Tensor, qparams: torch.Tensor, n: torch.Tensor, luv: torch.Tensor,
+                      gain: float = 1.0, normals_planar: bool = False,
+                      out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Diffuse gain for a quantised RGB HSH map under a normal map (``rti_relight_hsh8_gain``).  coef8, qparams, n,
+    luv, normals_planar and out_dtype as ``relight_hsh8_specular`` -> [E, P, 3]."""
+    api._require_cuda(coef8, "coef8")
+    if coef8.dim() != 3 or coef8.shape[1] != 3 or coef8.shape[2] not in (9, 16):
+        raise ValueError(f"coef8 must be [P, 3, 9] or [P, 3, 16]; got {tuple(coef8.shape)}")
+    _same_device(coef8=coef8, n=n)
+    if out_dtype not in api._ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    P = coef8.shape[0]
+    lu, lv = _specular_luv(luv)
+    out = coef8.new_empty((luv.shape[0], P, 3), dtype=out_dtype)
+    return api.relight_hsh8_gain_into(coef8.contiguous(), qparams.contiguous(), _specular_n(n, P, normals_planar),
+                                      lu, lv, out, basis=f"hsh{coef8.shape[2]}", gain=gain,
+                                      normal_layout="planar" if normals_planar else "pixel")
+
+
+@relight_hsh8_gain.register_fake
+def _(coef8, qparams, n, luv, gain=1.0, normals_planar=False, out_dtype=torch.float32):
     return coef8.new_empty((luv.shape[0], coef8.shape[0], 3), dtype=out_dtype)
