@@ -11,6 +11,7 @@
 #include <cmath>
 
 #include "rti_convert.h"
+#include "rti_dispatch.h"
 #include "rti_internal.h"
 #include "rti_ptm_px.h"
 #include "rti_shade.h"
@@ -142,12 +143,6 @@ inline int check_enhance(const char* entry, int mode, double gain, double kd, do
   return RTI_OK;
 }
 
-inline int check_enhance_out(const char* entry, int out_dtype) {
-  if (out_dtype != RTI_F32 && out_dtype != RTI_I32 && out_dtype != RTI_U8)
-    return fail(RTI_ERR_UNSUPPORTED, "%s: out dtype %d", entry, out_dtype);
-  return RTI_OK;
-}
-
 // the kernel argument: the half vector is wave-uniform, so light_frame forms it here
 inline Enhance enhance_args(double gain, double kd, double ks, int spec_exp, double lu, double lv) {
   const LightFrame f = light_frame(lu, lv);
@@ -156,24 +151,13 @@ inline Enhance enhance_args(double gain, double kd, double ks, int spec_exp, dou
 
 // f(mode tag, TO{}) for a checked mode and out_dtype: f is a generic lambda that launches the kernel instantiated
 // on decltype of its arguments
-template <int M>
-struct ModeTag {
-  static constexpr int value = M;
-};
-
 template <typename F>
 inline void with_mode_out(int mode, int out_dtype, F&& f) {
-  auto out = [&](auto m) {
-    switch (out_dtype) {
-      case RTI_F32: f(m, float{}); break;
-      case RTI_I32: f(m, int32_t{}); break;
-      default: f(m, uint8_t{}); break;
-    }
-  };
+  auto out = [&](auto m) { with_out(out_dtype, [&](auto t) { f(m, t); }); };
   if (mode == RTI_ENHANCE_SPECULAR)
-    out(ModeTag<RTI_ENHANCE_SPECULAR>{});
+    out(Tag<RTI_ENHANCE_SPECULAR>{});
   else
-    out(ModeTag<RTI_ENHANCE_DIFFUSE_GAIN>{});
+    out(Tag<RTI_ENHANCE_DIFFUSE_GAIN>{});
 }
 
 }  // namespace enhance_px

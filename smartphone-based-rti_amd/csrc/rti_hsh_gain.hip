@@ -22,6 +22,7 @@
 
 #include "rti_basis.h"
 #include "rti_convert.h"
+#include "rti_dispatch.h"
 #include "rti_hsh_render_px.h"
 #include "rti_stack.h"
 
@@ -202,14 +203,12 @@ void launch_c(const float* coef, int C, int layout, int64_t cs, int vin, const F
 // before the values of luv it counts); fills everything of `a` but the stream
 int check_frame(const char* entry, int64_t P, const float* normals, int normal_layout, double gain, const double* luv,
                 int E, void* out, int out_dtype, Frame& a) {
-  if (normal_layout != RTI_NORMAL_PIXEL_MAJOR && normal_layout != RTI_NORMAL_PLANAR)
-    return fail(RTI_ERR_BAD_ARG, "%s: normal layout %d", entry, normal_layout);
+  if (int st = check_normal_layout(entry, normal_layout)) return st;
   if (!std::isfinite(gain)) return fail(RTI_ERR_BAD_ARG, "%s: non-finite gain", entry);
   if (E < 1 || E > MAXE) return fail(RTI_ERR_BAD_ARG, "%s: E = %d outside [1, %d]", entry, E, MAXE);
   for (int i = 0; i < 2 * E; ++i)
     if (!std::isfinite(luv[i])) return fail(RTI_ERR_BAD_ARG, "%s: non-finite light direction", entry);
-  if (out_dtype != RTI_F32 && out_dtype != RTI_I32 && out_dtype != RTI_U8)
-    return fail(RTI_ERR_UNSUPPORTED, "%s: out dtype %d", entry, out_dtype);
+  if (int st = check_out_dtype(entry, out_dtype)) return st;
   a.P = P;
   a.normals = normals;
   a.nl = normal_layout;

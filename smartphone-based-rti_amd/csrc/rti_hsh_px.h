@@ -9,18 +9,18 @@
 #include <cstdint>
 
 #include "rti_internal.h"
-#include "rti_lrgb_px.h"
+#include "rti_wave_lds.h"
 
 namespace rti {
 namespace hsh_px {
 
-using lrgb_px::wave_lds_sync;
+using lds::wave_lds_sync;
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 inline bool hsh_basis(int basis) { return basis == RTI_BASIS_HSH9 || basis == RTI_BASIS_HSH16; }
 
-// rti_relight.hip's dot_k for fp32: fused multiply-adds in term order.  A copy, as rti_lrgb_px.h's loads are:
+// rti_relight.hip's dot_k for fp32: fused multiply-adds in term order.  A copy, as rti_lane4.h's loads are:
 // bench.py hashes rti_relight.hip to decide whether profiles/traffic.json is stale.
 template <int K>
 __device__ __forceinline__ float dot_k(const float (&c)[K], const float* b) {

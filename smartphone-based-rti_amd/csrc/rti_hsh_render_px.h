@@ -102,15 +102,5 @@ inline int rows_as_dwords(const void* out, int out_dtype, int64_t P) {
   return aligned_to(out, 4) && (out_dtype != RTI_U8 || P % 4 == 0) ? 1 : 0;
 }
 
-// f(TO{}) with TO the output type (after the entry's check of out_dtype)
-template <typename F>
-inline void with_out(int out_dtype, F&& f) {
-  switch (out_dtype) {
-    case RTI_F32: f(float{}); break;
-    case RTI_I32: f(int32_t{}); break;
-    default: f(uint8_t{}); break;
-  }
-}
-
 }  // namespace hsh_render
 }  // namespace rti

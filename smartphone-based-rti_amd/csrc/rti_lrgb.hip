@@ -33,15 +33,16 @@
 
 #include "rti_basis.h"
 #include "rti_convert.h"
+#include "rti_dispatch.h"
 #include "rti_enhance_px.h"
+#include "rti_lane4.h"
 #include "rti_lrgb_px.h"
-#include "rti_quant8.h"
-#include "rti_stack.h"
 
 namespace rti {
 namespace {
 
-using namespace lrgb_px;  // K, NL, dot6, rgb_of and the wave loads and stores, shared with rti_lrgb8.hip
+using namespace lrgb_px;  // K, NL, dot6, rgb_of, shared with rti_lrgb8.hip
+using namespace lane4;    // the wave loads, the staged row store and the RGB sink
 
 // ---- per-pixel arithmetic (fp64, no contraction; tests/lrgb_ref.py restates it line by line) ------------------
 
@@ -92,7 +93,7 @@ __device__ __forceinline__ void lrgb_of(const float (&xr)[K], const float (&xg)[
   for (int j = 0; j < K; ++j) o[j] = finite ? (float)a[j] : NAN;
 }
 
-// dot6, rgb_of (the relight's per-pixel arithmetic) and the wave loads and stores: rti_lrgb_px.h
+// dot6, rgb_of (the relight's per-pixel arithmetic): rti_lrgb_px.h
 
 // ---- kernels ------------------------------------------------------------------------------------------------------
 // Both: a wave owns pixels [wave_px, wave_px + 256).  vec != 0 (P % 4 == 0, every pointer aligned for its vector
@@ -142,8 +143,7 @@ template <int CL, typename TO>
 __global__ void __launch_bounds__(256)
 relight_lrgb_k(const float* __restrict__ lrgb, int64_t P, int vec, const double* __restrict__ luv, int E,
                TO* __restrict__ out) {
-  constexpr bool STAGE_OUT = sizeof(TO) == 4;  // fp32 / int32: 48 B per lane through the slab
-  constexpr int SLAB = slab_v4(CL == RTI_COEF_PIXEL_MAJOR ? NL : 0, STAGE_OUT ? 3 : 0);
+  constexpr int SLAB = slab_v4(CL == RTI_COEF_PIXEL_MAJOR ? NL : 0, rgb_staged<TO>() ? 3 : 0);
   __shared__ floatx4 slabs[4 * SLAB];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
@@ -159,9 +159,10 @@ relight_lrgb_k(const float* __restrict__ lrgb, int64_t P, int vec, const double*
 #pragma unroll
       for (int v = 0; v < 4; ++v) rgb_of<TO>(m[v], b, o[v]);
       TO* rows = out + ((int64_t)e * P + wave_px) * 3;
-      if constexpr (STAGE_OUT) {
+      if constexpr (rgb_staged<TO>()) {
         store_rows_staged<3, TO>(rows, lane, slab, o);
-      } else {  // uint8: a lane's 12 bytes as three dwords
+      } else {  // uint8: a lane's 12 bytes as three dwords, packed here: with store_rgb4 the pixel-major uint8
+                // instantiation missed the A/B bound by 0.05 us (profiles/lane4_ab.json), so this body stays
         uint32_t* o4 = reinterpret_cast<uint32_t*>(rows + 12 * lane);
         const uint8_t* f = &o[0][0];
 #pragma unroll
@@ -195,8 +196,7 @@ template <int CL, typename TO, int MODE>
 __global__ void __launch_bounds__(256)
 relight_lrgb_enhanced_k(const float* __restrict__ lrgb, int64_t P, int vec, enhance_px::Enhance q,
                         TO* __restrict__ out) {
-  constexpr bool STAGE_OUT = sizeof(TO) == 4;  // fp32 / int32: 48 B per lane through the slab
-  constexpr int SLAB = slab_v4(CL == RTI_COEF_PIXEL_MAJOR ? NL : 0, STAGE_OUT ? 3 : 0);
+  constexpr int SLAB = slab_v4(CL == RTI_COEF_PIXEL_MAJOR ? NL : 0, rgb_staged<TO>() ? 3 : 0);
   __shared__ floatx4 slabs[4 * SLAB];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
@@ -208,11 +208,7 @@ relight_lrgb_enhanced_k(const float* __restrict__ lrgb, int64_t P, int vec, enha
     TO o[4][3];
 #pragma unroll
     for (int v = 0; v < 4; ++v) enhance_px::lrgb_enhanced<MODE, TO>(m[v], q, o[v]);
-    TO* rows = out + wave_px * 3;
-    if constexpr (STAGE_OUT)
-      store_rows_staged<3, TO>(rows, lane, slab, o);
-    else
-      quant8::store_dwords<12>(rows + 12 * lane, &o[0][0]);
+    store_rgb4<TO>(out + wave_px * 3, lane, slab, o);
     return;
   }
   for (int j = 0; j < 4; ++j) {
@@ -227,63 +223,10 @@ relight_lrgb_enhanced_k(const float* __restrict__ lrgb, int64_t P, int vec, enha
   }
 }
 
-// ---- launchers ----------------------------------------------------------------------------------------------------
-
-struct CompressArgs {
-  const float* coef;
-  int64_t cstride, P;
-  int vec;
-  Colour q;
-  float* lrgb;
-  hipStream_t s;
-};
-
-template <int CL, int OL>
-void launch_compress_t(const CompressArgs& a) {
-  hipLaunchKernelGGL((lrgb_from_rgb_k<CL, OL>), dim3(grid_1d(a.P, 1024)), dim3(256), 0, a.s, a.coef, a.cstride, a.P,
-                     a.vec, a.q, a.lrgb);
-}
-
-template <int CL>
-void launch_compress_ol(const CompressArgs& a, int ol) {
-  if (ol == RTI_COEF_PLANAR)
-    launch_compress_t<CL, RTI_COEF_PLANAR>(a);
-  else
-    launch_compress_t<CL, RTI_COEF_PIXEL_MAJOR>(a);
-}
-
-struct RelightArgs {
-  const float* lrgb;
-  int64_t P;
-  int vec;
-  const double* luv;
-  int E;
-  void* out;
-  hipStream_t s;
-};
-
-template <int CL, typename TO>
-void launch_relight_t(const RelightArgs& a) {
-  hipLaunchKernelGGL((relight_lrgb_k<CL, TO>), dim3(grid_1d(a.P, 1024)), dim3(256), 0, a.s, a.lrgb, a.P, a.vec, a.luv,
-                     a.E, static_cast<TO*>(a.out));
-}
-
-template <int CL>
-void launch_relight_out(const RelightArgs& a, int odt) {
-  switch (odt) {
-    case RTI_F32: launch_relight_t<CL, float>(a); break;
-    case RTI_I32: launch_relight_t<CL, int32_t>(a); break;
-    default: launch_relight_t<CL, uint8_t>(a); break;
-  }
-}
-
-template <int CL>
-void launch_enhanced_t(const RelightArgs& a, const enhance_px::Enhance& q, int mode, int odt) {
-  enhance_px::with_mode_out(mode, odt, [&](auto m, auto t) {
-    using TO = decltype(t);
-    hipLaunchKernelGGL((relight_lrgb_enhanced_k<CL, TO, decltype(m)::value>), dim3(grid_1d(a.P, 1024)), dim3(256), 0,
-                       a.s, a.lrgb, a.P, a.vec, q, static_cast<TO*>(a.out));
-  });
+int check_lrgb_layout(const char* entry, int layout) {
+  if (layout != RTI_COEF_PIXEL_MAJOR && layout != RTI_COEF_PLANAR)
+    return fail(RTI_ERR_BAD_ARG, "%s: lrgb layout %d", entry, layout);
+  return RTI_OK;
 }
 
 }  // namespace
@@ -298,28 +241,29 @@ extern "C" int rti_lrgb_from_rgb(const float* coef, int coef_layout, int64_t coe
   if (int st = check_pointers(E, {coef, gram, lrgb})) return st;
   if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", E);
   if (int st = check_coef_layout(E, coef_layout)) return st;
-  if (lrgb_layout != RTI_COEF_PIXEL_MAJOR && lrgb_layout != RTI_COEF_PLANAR)
-    return fail(RTI_ERR_BAD_ARG, "%s: lrgb layout %d", E, lrgb_layout);
+  if (int st = check_lrgb_layout(E, lrgb_layout)) return st;
   const CoefSource src = coef_view(coef, coef_layout, K, P, coef_channel_stride);
   if (int st = check_coef_stride(E, src, P, 3)) return st;
-  CompressArgs a{coef, src.ocstride, P, 0, {}, lrgb, (hipStream_t)stream};
+  Colour q;
   for (int i = 0; i < K * K; ++i) {
     if (!std::isfinite(gram[i])) return fail(RTI_ERR_BAD_ARG, "%s: non-finite gram entry %d", E, i);
-    a.q.G[i / K][i % K] = gram[i];
+    q.G[i / K][i % K] = gram[i];
   }
   double wsum = 0.0;
   for (int c = 0; c < 3; ++c) {
     const double w = weights ? weights[c] : 1.0 / 3.0;
     if (!std::isfinite(w) || w < 0.0) return fail(RTI_ERR_BAD_ARG, "%s: weight %d is negative or not finite", E, c);
-    a.q.w[c] = w;
+    q.w[c] = w;
     wsum += w;
   }
   if (!(wsum > 0.0)) return fail(RTI_ERR_BAD_ARG, "%s: the weights are all zero", E);
-  a.vec = P % 4 == 0 && coef_vec_ok_any_c(src) && aligned_to(lrgb, 16) ? 1 : 0;
-  if (coef_layout == RTI_COEF_PLANAR)
-    launch_compress_ol<RTI_COEF_PLANAR>(a, lrgb_layout);
-  else
-    launch_compress_ol<RTI_COEF_PIXEL_MAJOR>(a, lrgb_layout);
+  const int vec = P % 4 == 0 && coef_vec_ok_any_c(src) && aligned_to(lrgb, 16) ? 1 : 0;
+  with_layout(coef_layout, [&](auto cl) {
+    with_layout(lrgb_layout, [&](auto ol) {
+      launch(lrgb_from_rgb_k<decltype(cl)::value, decltype(ol)::value>, P, (hipStream_t)stream, coef, src.ocstride, P,
+             vec, q, lrgb);
+    });
+  });
   return check_launch(E);
 }
 
@@ -328,17 +272,14 @@ extern "C" int rti_relight_lrgb(const float* lrgb, int lrgb_layout, int64_t P, c
   const char* const E = "rti_relight_lrgb";
   if (int st = check_pointers(E, {lrgb, luv, out})) return st;
   if (P < 1 || E_ < 1) return fail(RTI_ERR_BAD_ARG, "%s: P and E must be positive", E);
-  if (lrgb_layout != RTI_COEF_PIXEL_MAJOR && lrgb_layout != RTI_COEF_PLANAR)
-    return fail(RTI_ERR_BAD_ARG, "%s: lrgb layout %d", E, lrgb_layout);
-  if (out_dtype != RTI_F32 && out_dtype != RTI_I32 && out_dtype != RTI_U8)
-    return fail(RTI_ERR_UNSUPPORTED, "%s: out dtype %d", E, out_dtype);
-  const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // a lane's dword / the wave's 16-byte pieces
-  const bool vec = P % 4 == 0 && aligned_to(lrgb, 16) && aligned_to(out, ovec);
-  const RelightArgs a{lrgb, P, vec ? 1 : 0, luv, E_, out, (hipStream_t)stream};
-  if (lrgb_layout == RTI_COEF_PLANAR)
-    launch_relight_out<RTI_COEF_PLANAR>(a, out_dtype);
-  else
-    launch_relight_out<RTI_COEF_PIXEL_MAJOR>(a, out_dtype);
+  if (int st = check_lrgb_layout(E, lrgb_layout)) return st;
+  if (int st = check_out_dtype(E, out_dtype)) return st;
+  const int vec = P % 4 == 0 && aligned_to(lrgb, 16) && rgb_out_vec(out, out_dtype) ? 1 : 0;
+  with_layout(lrgb_layout, [&](auto cl) {
+    with_out(out_dtype, [&](auto t) {
+      launch(relight_lrgb_k<decltype(cl)::value, decltype(t)>, P, (hipStream_t)stream, lrgb, P, vec, luv, E_, out);
+    });
+  });
   return check_launch(E);
 }
 
@@ -348,18 +289,17 @@ extern "C" int rti_relight_lrgb_enhanced(const float* lrgb, int lrgb_layout, int
   const char* const E = "rti_relight_lrgb_enhanced";
   if (int st = check_pointers(E, {lrgb, out})) return st;
   if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", E);
-  if (lrgb_layout != RTI_COEF_PIXEL_MAJOR && lrgb_layout != RTI_COEF_PLANAR)
-    return fail(RTI_ERR_BAD_ARG, "%s: lrgb layout %d", E, lrgb_layout);
+  if (int st = check_lrgb_layout(E, lrgb_layout)) return st;
   if (int st = enhance_px::check_enhance(E, mode, gain, kd, ks, spec_exp, lu, lv)) return st;
-  if (int st = enhance_px::check_enhance_out(E, out_dtype)) return st;
-  const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // a lane's dword / the wave's 16-byte pieces
-  const bool vec = P % 4 == 0 && aligned_to(lrgb, 16) && aligned_to(out, ovec);
-  const RelightArgs a{lrgb, P, vec ? 1 : 0, nullptr, 1, out, (hipStream_t)stream};
+  if (int st = check_out_dtype(E, out_dtype)) return st;
+  const int vec = P % 4 == 0 && aligned_to(lrgb, 16) && rgb_out_vec(out, out_dtype) ? 1 : 0;
   const enhance_px::Enhance q = enhance_px::enhance_args(gain, kd, ks, spec_exp, lu, lv);
   note_launches(1);
-  if (lrgb_layout == RTI_COEF_PLANAR)
-    launch_enhanced_t<RTI_COEF_PLANAR>(a, q, mode, out_dtype);
-  else
-    launch_enhanced_t<RTI_COEF_PIXEL_MAJOR>(a, q, mode, out_dtype);
+  with_layout(lrgb_layout, [&](auto cl) {
+    enhance_px::with_mode_out(mode, out_dtype, [&](auto m, auto t) {
+      launch(relight_lrgb_enhanced_k<decltype(cl)::value, decltype(t), decltype(m)::value>, P, (hipStream_t)stream,
+             lrgb, P, vec, q, out);
+    });
+  });
   return check_launch(E);
 }

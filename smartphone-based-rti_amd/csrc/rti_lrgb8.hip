@@ -25,15 +25,17 @@
 
 #include "rti_basis.h"
 #include "rti_convert.h"
+#include "rti_dispatch.h"
 #include "rti_enhance_px.h"
+#include "rti_lane4.h"
 #include "rti_lrgb_px.h"
 #include "rti_quant8.h"
-#include "rti_stack.h"
 
 namespace rti {
 namespace {
 
 using namespace lrgb_px;
+using namespace lane4;  // the wave loads of the fp32 map, the byte sources, the tables and the RGB sink
 using namespace quant8;
 
 constexpr int NQ = 2 * K + 1;  // a partial: lo[6], hi[6], the chroma max; qparams: scale[6], bias[6], s
@@ -164,8 +166,7 @@ template <typename TO>
 __global__ void __launch_bounds__(256)
 relight_lrgb8_k(const uint8_t* __restrict__ coef8, const uint8_t* __restrict__ rgb8, int64_t P, int vec,
                 const double* __restrict__ qparams, const double* __restrict__ luv, int E, TO* __restrict__ out) {
-  constexpr bool STAGE_OUT = sizeof(TO) == 4;  // fp32 / int32: 48 B per lane through the slab
-  constexpr int SLAB = slab_v4(0, STAGE_OUT ? 3 : 0);
+  constexpr int SLAB = slab_v4(0, rgb_staged<TO>() ? 3 : 0);
   __shared__ floatx4 slabs[4 * SLAB];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
@@ -174,24 +175,11 @@ relight_lrgb8_k(const uint8_t* __restrict__ coef8, const uint8_t* __restrict__ r
   const QParams<K> q = load_qparams<K>(qparams);  // s is not used: the colour bytes are chroma·255
   if (vec && wave_px + 256 <= P) {                // wave-uniform
     const int64_t p0 = wave_px + 4 * lane;
-    union {
-      u32x2 v[3];
-      uint8_t b[4][K];
-    } cb;
-    union {
-      uint32_t v[3];
-      uint8_t b[4][3];
-    } rb;
-    const u32x2* c2 = reinterpret_cast<const u32x2*>(coef8 + p0 * K);
-    const uint32_t* r4 = reinterpret_cast<const uint32_t*>(rgb8 + p0 * 3);
-#pragma unroll
-    for (int w = 0; w < 3; ++w) {
-      cb.v[w] = c2[w];
-      rb.v[w] = r4[w];
-    }
+    Lrgb8Px r;
+    load_bytes4(coef8, rgb8, p0, r);
     float m[4][NL];
 #pragma unroll
-    for (int v = 0; v < 4; ++v) dequantise_px(cb.b[v], rb.b[v], q, m[v]);
+    for (int v = 0; v < 4; ++v) dequantise_px(r.cb.b[v], r.rb.b[v], q, m[v]);
     for (int e = 0; e < E; ++e) {
       double b[K];
       ptm_eval<double>(luv[2 * e], luv[2 * e + 1], b);
@@ -199,10 +187,7 @@ relight_lrgb8_k(const uint8_t* __restrict__ coef8, const uint8_t* __restrict__ r
 #pragma unroll
       for (int v = 0; v < 4; ++v) rgb_of<TO>(m[v], b, o[v]);
       TO* rows = out + ((int64_t)e * P + wave_px) * 3;
-      if constexpr (STAGE_OUT)
-        store_rows_staged<3, TO>(rows, lane, slab, o);
-      else
-        store_dwords<12>(rows + 12 * lane, &o[0][0]);
+      store_rgb4<TO>(rows, lane, slab, o);
     }
     return;
   }
@@ -210,10 +195,7 @@ relight_lrgb8_k(const uint8_t* __restrict__ coef8, const uint8_t* __restrict__ r
     const int64_t p = wave_px + 64 * j + lane;
     if (p >= P) break;
     uint8_t cb[K], rb[3];
-#pragma unroll
-    for (int i = 0; i < K; ++i) cb[i] = coef8[p * K + i];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) rb[c] = rgb8[p * 3 + c];
+    load_bytes1(coef8, rgb8, p, cb, rb);
     float m[NL];
     dequantise_px(cb, rb, q, m);
     for (int e = 0; e < E; ++e) {
@@ -228,28 +210,11 @@ relight_lrgb8_k(const uint8_t* __restrict__ coef8, const uint8_t* __restrict__ r
   }
 }
 
-template <typename TO>
-void launch_relight8(const uint8_t* coef8, const uint8_t* rgb8, int64_t P, int vec, const double* qparams,
-                     const double* luv, int E, void* out, hipStream_t s) {
-  hipLaunchKernelGGL((relight_lrgb8_k<TO>), dim3(grid_1d(P, 1024)), dim3(256), 0, s, coef8, rgb8, P, vec, qparams,
-                     luv, E, static_cast<TO*>(out));
-}
-
 // ---- enhanced rendering from the bytes ---------------------------------------------------------
 // A byte can only become one of 256 fp32 values, so the workgroup fills seven 256-entry tables in LDS (7 KiB; lane t
-// forms entry t of each in fp64 and rounds it once: rti_rgb8.hip's fill_tables plus the chroma's byte / 255) and a
+// forms entry t of each in fp64 and rounds it once: rti_lane4.h's fill_tables<7>, the seventh the chroma's byte / 255) and a
 // pixel costs 9 LDS reads instead of six fp64 products and three fp64 divisions.  The tables hold the very values
 // dequantise_px gives, so the image is rti_relight_lrgb_enhanced's of the dequantised map bit for bit.
-
-constexpr int TAB = 256;
-
-__device__ __forceinline__ void fill_tables(const double* __restrict__ qparams, float* __restrict__ tab) {
-#pragma clang fp contract(off)
-  const double t = (double)threadIdx.x;
-#pragma unroll
-  for (int j = 0; j < K; ++j) tab[j * TAB + threadIdx.x] = (float)((t - qparams[K + j]) * qparams[j]);
-  tab[K * TAB + threadIdx.x] = (float)(t / 255.0);
-}
 
 __device__ __forceinline__ void lookup_px(const uint8_t (&cb)[K], const uint8_t (&rb)[3], const float* __restrict__ tab,
                                           float (&m)[NL]) {
@@ -263,11 +228,10 @@ template <typename TO, int MODE>
 __global__ void __launch_bounds__(256)
 relight_lrgb8_enhanced_k(const uint8_t* __restrict__ coef8, const uint8_t* __restrict__ rgb8, int64_t P, int vec,
                          const double* __restrict__ qparams, enhance_px::Enhance q, TO* __restrict__ out) {
-  constexpr bool STAGE_OUT = sizeof(TO) == 4;  // fp32 / int32: 48 B per lane through the slab
-  constexpr int SLAB = slab_v4(0, STAGE_OUT ? 3 : 0);
+  constexpr int SLAB = slab_v4(0, rgb_staged<TO>() ? 3 : 0);
   __shared__ floatx4 slabs[4 * SLAB];
   __shared__ float tab[(K + 1) * TAB];
-  fill_tables(qparams, tab);
+  fill_tables<K + 1>(qparams, tab);
   __syncthreads();  // the one workgroup barrier: waves may leave below
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
@@ -275,43 +239,24 @@ relight_lrgb8_enhanced_k(const uint8_t* __restrict__ coef8, const uint8_t* __res
   floatx4* slab = slabs + wave * SLAB;
   if (vec && wave_px + 256 <= P) {  // wave-uniform
     const int64_t p0 = wave_px + 4 * lane;
-    union {
-      u32x2 v[3];
-      uint8_t b[4][K];
-    } cb;
-    union {
-      uint32_t v[3];
-      uint8_t b[4][3];
-    } rb;
-    const u32x2* c2 = reinterpret_cast<const u32x2*>(coef8 + p0 * K);
-    const uint32_t* r4 = reinterpret_cast<const uint32_t*>(rgb8 + p0 * 3);
-#pragma unroll
-    for (int w = 0; w < 3; ++w) {
-      cb.v[w] = c2[w];
-      rb.v[w] = r4[w];
-    }
+    Lrgb8Px r;
+    load_bytes4(coef8, rgb8, p0, r);
     TO o[4][3];
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
       float m[NL];
-      lookup_px(cb.b[v], rb.b[v], tab, m);
+      lookup_px(r.cb.b[v], r.rb.b[v], tab, m);
       enhance_px::lrgb_enhanced<MODE, TO>(m, q, o[v]);
     }
     TO* rows = out + wave_px * 3;
-    if constexpr (STAGE_OUT)
-      store_rows_staged<3, TO>(rows, lane, slab, o);
-    else
-      store_dwords<12>(rows + 12 * lane, &o[0][0]);
+    store_rgb4<TO>(rows, lane, slab, o);
     return;
   }
   for (int j = 0; j < 4; ++j) {
     const int64_t p = wave_px + 64 * j + lane;
     if (p >= P) break;
     uint8_t cb[K], rb[3];
-#pragma unroll
-    for (int i = 0; i < K; ++i) cb[i] = coef8[p * K + i];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) rb[c] = rgb8[p * 3 + c];
+    load_bytes1(coef8, rgb8, p, cb, rb);
     float m[NL];
     lookup_px(cb, rb, tab, m);
     TO o[3];
@@ -348,12 +293,10 @@ extern "C" int rti_lrgb_qparams(const float* lrgb, int lrgb_layout, int64_t P, v
   const int vec = P % 4 == 0 && aligned_to(lrgb, 16) ? 1 : 0;
   float* partial = static_cast<float*>(workspace);
   note_launches(2);
-  if (lrgb_layout == RTI_COEF_PLANAR)
-    hipLaunchKernelGGL((lrgb_extremes_k<RTI_COEF_PLANAR>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, lrgb, P,
+  with_layout(lrgb_layout, [&](auto cl) {
+    hipLaunchKernelGGL((lrgb_extremes_k<decltype(cl)::value>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, lrgb, P,
                        vec, partial);
-  else
-    hipLaunchKernelGGL((lrgb_extremes_k<RTI_COEF_PIXEL_MAJOR>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, lrgb,
-                       P, vec, partial);
+  });
   if (int st = check_launch(E)) return st;
   hipLaunchKernelGGL(lrgb_qparams_k, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, blocks, qparams);
   return check_launch(E);
@@ -365,15 +308,12 @@ extern "C" int rti_lrgb_quantise(const float* lrgb, int lrgb_layout, int64_t P, 
   if (int st = check_pointers(E, {lrgb, qparams, coef8, rgb8})) return st;
   if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", E);
   if (int st = check_lrgb_layout(E, lrgb_layout)) return st;
-  if (!aligned_to(qparams, 8)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 8-byte aligned", E);
+  if (int st = check_qparams_aligned(E, qparams)) return st;
   const int vec = P % 4 == 0 && aligned_to(lrgb, 16) && aligned_to(coef8, 4) && aligned_to(rgb8, 4) ? 1 : 0;
   note_launches(1);
-  if (lrgb_layout == RTI_COEF_PLANAR)
-    hipLaunchKernelGGL((lrgb_quantise_k<RTI_COEF_PLANAR>), dim3(grid_1d(P, 1024)), dim3(256), 0, (hipStream_t)stream,
-                       lrgb, P, vec, qparams, coef8, rgb8);
-  else
-    hipLaunchKernelGGL((lrgb_quantise_k<RTI_COEF_PIXEL_MAJOR>), dim3(grid_1d(P, 1024)), dim3(256), 0,
-                       (hipStream_t)stream, lrgb, P, vec, qparams, coef8, rgb8);
+  with_layout(lrgb_layout, [&](auto cl) {
+    launch(lrgb_quantise_k<decltype(cl)::value>, P, (hipStream_t)stream, lrgb, P, vec, qparams, coef8, rgb8);
+  });
   return check_launch(E);
 }
 
@@ -382,17 +322,13 @@ extern "C" int rti_relight_lrgb8(const uint8_t* coef8, const uint8_t* rgb8, int6
   const char* const E = "rti_relight_lrgb8";
   if (int st = check_pointers(E, {coef8, rgb8, qparams, luv, out})) return st;
   if (P < 1 || E_ < 1) return fail(RTI_ERR_BAD_ARG, "%s: P and E must be positive", E);
-  if (out_dtype != RTI_F32 && out_dtype != RTI_I32 && out_dtype != RTI_U8)
-    return fail(RTI_ERR_UNSUPPORTED, "%s: out dtype %d", E, out_dtype);
-  if (!aligned_to(qparams, 8)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 8-byte aligned", E);
-  const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // a lane's dword / the wave's 16-byte pieces
-  const int vec = P % 4 == 0 && aligned_to(coef8, 8) && aligned_to(rgb8, 4) && aligned_to(out, ovec) ? 1 : 0;
+  if (int st = check_out_dtype(E, out_dtype)) return st;
+  if (int st = check_qparams_aligned(E, qparams)) return st;
+  const int vec = P % 4 == 0 && aligned_to(coef8, 8) && aligned_to(rgb8, 4) && rgb_out_vec(out, out_dtype) ? 1 : 0;
   note_launches(1);
-  switch (out_dtype) {
-    case RTI_F32: launch_relight8<float>(coef8, rgb8, P, vec, qparams, luv, E_, out, (hipStream_t)stream); break;
-    case RTI_I32: launch_relight8<int32_t>(coef8, rgb8, P, vec, qparams, luv, E_, out, (hipStream_t)stream); break;
-    default: launch_relight8<uint8_t>(coef8, rgb8, P, vec, qparams, luv, E_, out, (hipStream_t)stream); break;
-  }
+  with_out(out_dtype, [&](auto t) {
+    launch(relight_lrgb8_k<decltype(t)>, P, (hipStream_t)stream, coef8, rgb8, P, vec, qparams, luv, E_, out);
+  });
   return check_launch(E);
 }
 
@@ -403,16 +339,14 @@ extern "C" int rti_relight_lrgb8_enhanced(const uint8_t* coef8, const uint8_t* r
   if (int st = check_pointers(E, {coef8, rgb8, qparams, out})) return st;
   if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", E);
   if (int st = enhance_px::check_enhance(E, mode, gain, kd, ks, spec_exp, lu, lv)) return st;
-  if (int st = enhance_px::check_enhance_out(E, out_dtype)) return st;
-  if (!aligned_to(qparams, 8)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 8-byte aligned", E);
-  const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // a lane's dword / the wave's 16-byte pieces
-  const int vec = P % 4 == 0 && aligned_to(coef8, 8) && aligned_to(rgb8, 4) && aligned_to(out, ovec) ? 1 : 0;
+  if (int st = check_out_dtype(E, out_dtype)) return st;
+  if (int st = check_qparams_aligned(E, qparams)) return st;
+  const int vec = P % 4 == 0 && aligned_to(coef8, 8) && aligned_to(rgb8, 4) && rgb_out_vec(out, out_dtype) ? 1 : 0;
   const enhance_px::Enhance q = enhance_px::enhance_args(gain, kd, ks, spec_exp, lu, lv);
   note_launches(1);
   enhance_px::with_mode_out(mode, out_dtype, [&](auto m, auto t) {
-    using TO = decltype(t);
-    hipLaunchKernelGGL((relight_lrgb8_enhanced_k<TO, decltype(m)::value>), dim3(grid_1d(P, 1024)), dim3(256), 0,
-                       (hipStream_t)stream, coef8, rgb8, P, vec, qparams, q, static_cast<TO*>(out));
+    launch(relight_lrgb8_enhanced_k<decltype(t), decltype(m)::value>, P, (hipStream_t)stream, coef8, rgb8, P, vec,
+           qparams, q, out);
   });
   return check_launch(E);
 }

@@ -33,7 +33,9 @@
 #include <type_traits>
 
 #include "rti_convert.h"
+#include "rti_dispatch.h"
 #include "rti_enhance_px.h"
+#include "rti_lane4.h"
 #include "rti_ptm_px.h"
 #include "rti_stack.h"
 
@@ -44,11 +46,7 @@ using namespace ptm_px;      // K = 6 and rti_ptm_normals' per-pixel function, s
 using namespace enhance_px;  // rti_relight_enhanced's, shared with the colour forms
 typedef double doublex2 __attribute__((ext_vector_type(2)));
 
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
+using lane4::wave_lds_sync;
 
 // ---- per-pixel arithmetic: ptm_value, ptm_peak and ptm_normal in rti_ptm_px.h; diffuse_gain_value, Enhance and
 // enhanced_value in rti_enhance_px.h, shared with the colour forms
@@ -212,78 +210,7 @@ relight_enhanced_k(const TC* __restrict__ coef, int64_t P, int vec, Enhance q, T
   }
 }
 
-// ---- launchers ------------------------------------------------------------------------------------------------
-
-struct NormalsArgs {
-  const void* coef;
-  int64_t P;
-  int vec;
-  float* normals;
-  uint8_t* kind;
-  float* peak;
-  hipStream_t s;
-};
-
-template <typename TC, int CL, int NL>
-void launch_normals_t(const NormalsArgs& a) {
-  hipLaunchKernelGGL((ptm_normals_k<TC, CL, NL>), dim3(grid_1d(a.P, 1024)), dim3(256), 0, a.s,
-                     static_cast<const TC*>(a.coef), a.P, a.vec, a.normals, a.kind, a.peak);
-}
-
-template <typename TC, int CL>
-void launch_normals_nl(const NormalsArgs& a, int nl) {
-  if (nl == RTI_NORMAL_PLANAR)
-    launch_normals_t<TC, CL, RTI_NORMAL_PLANAR>(a);
-  else
-    launch_normals_t<TC, CL, RTI_NORMAL_PIXEL_MAJOR>(a);
-}
-
-template <typename TC>
-void launch_normals_cl(const NormalsArgs& a, int cl, int nl) {
-  if (cl == RTI_COEF_PLANAR)
-    launch_normals_nl<TC, RTI_COEF_PLANAR>(a, nl);
-  else
-    launch_normals_nl<TC, RTI_COEF_PIXEL_MAJOR>(a, nl);
-}
-
-struct EnhanceArgs {
-  const void* coef;
-  int64_t P;
-  int vec;
-  Enhance q;
-  void* out;
-  hipStream_t s;
-};
-
-template <typename TC, int CL, typename TO>
-void launch_enhanced_t(const EnhanceArgs& a, int mode) {
-  const dim3 grid(grid_1d(a.P, 1024));
-  const TC* coef = static_cast<const TC*>(a.coef);
-  TO* out = static_cast<TO*>(a.out);
-  if (mode == RTI_ENHANCE_SPECULAR)
-    hipLaunchKernelGGL((relight_enhanced_k<TC, CL, TO, RTI_ENHANCE_SPECULAR>), grid, dim3(256), 0, a.s, coef, a.P, a.vec,
-                       a.q, out);
-  else
-    hipLaunchKernelGGL((relight_enhanced_k<TC, CL, TO, RTI_ENHANCE_DIFFUSE_GAIN>), grid, dim3(256), 0, a.s, coef, a.P,
-                       a.vec, a.q, out);
-}
-
-template <typename TC, int CL>
-void launch_enhanced_out(const EnhanceArgs& a, int mode, int odt) {
-  switch (odt) {
-    case RTI_F32: launch_enhanced_t<TC, CL, float>(a, mode); break;
-    case RTI_I32: launch_enhanced_t<TC, CL, int32_t>(a, mode); break;
-    default: launch_enhanced_t<TC, CL, uint8_t>(a, mode); break;
-  }
-}
-
-template <typename TC>
-void launch_enhanced_cl(const EnhanceArgs& a, int cl, int mode, int odt) {
-  if (cl == RTI_COEF_PLANAR)
-    launch_enhanced_out<TC, RTI_COEF_PLANAR>(a, mode, odt);
-  else
-    launch_enhanced_out<TC, RTI_COEF_PIXEL_MAJOR>(a, mode, odt);
-}
+// ---- checks --------------------------------------------------------------------------------------------------
 
 // the checks the two entries share, in the order include/rti.h documents them
 int check_ptm_map(const char* entry, int64_t P, int coef_layout) {
@@ -308,16 +235,17 @@ extern "C" int rti_ptm_normals(const void* coef, int coef_dtype, int basis, int 
   const char* const E = "rti_ptm_normals";
   if (int st = check_pointers(E, {coef, normals})) return st;
   if (int st = check_ptm_map(E, P, coef_layout)) return st;
-  if (normal_layout != RTI_NORMAL_PIXEL_MAJOR && normal_layout != RTI_NORMAL_PLANAR)
-    return fail(RTI_ERR_BAD_ARG, "%s: normal layout %d", E, normal_layout);
+  if (int st = check_normal_layout(E, normal_layout)) return st;
   if (int st = check_ptm_types(E, basis, coef_dtype)) return st;
-  const bool vec = P % 4 == 0 && aligned_to(coef, 16) && aligned_to(normals, 16) && (!kind || aligned_to(kind, 4)) &&
-                   (!peak || aligned_to(peak, 16));
-  const NormalsArgs a{coef, P, vec ? 1 : 0, normals, kind, peak, (hipStream_t)stream};
-  if (coef_dtype == RTI_F64)
-    launch_normals_cl<double>(a, coef_layout, normal_layout);
-  else
-    launch_normals_cl<float>(a, coef_layout, normal_layout);
+  const int vec = P % 4 == 0 && aligned_to(coef, 16) && normals_out_vec(normals, kind, peak) ? 1 : 0;
+  with_coef_dtype(coef_dtype, [&](auto c) {
+    with_layout(coef_layout, [&](auto cl) {
+      with_normal_layout(normal_layout, [&](auto nl) {
+        lane4::launch(ptm_normals_k<decltype(c), decltype(cl)::value, decltype(nl)::value>, P, (hipStream_t)stream, coef,
+                      P, vec, normals, kind, peak);
+      });
+    });
+  });
   return check_launch(E);
 }
 
@@ -329,14 +257,16 @@ extern "C" int rti_relight_enhanced(const void* coef, int coef_dtype, int basis,
   if (int st = check_ptm_map(E, P, coef_layout)) return st;
   if (int st = check_enhance(E, mode, gain, kd, ks, spec_exp, lu, lv)) return st;
   if (int st = check_ptm_types(E, basis, coef_dtype)) return st;
-  if (int st = check_enhance_out(E, out_dtype)) return st;
-  const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // bytes of a lane's 4 outputs
-  const bool vec = P % 4 == 0 && aligned_to(coef, 16) && aligned_to(out, ovec);
-  const EnhanceArgs a{coef, P, vec ? 1 : 0, enhance_args(gain, kd, ks, spec_exp, lu, lv), out,
-                      (hipStream_t)stream};
-  if (coef_dtype == RTI_F64)
-    launch_enhanced_cl<double>(a, coef_layout, mode, out_dtype);
-  else
-    launch_enhanced_cl<float>(a, coef_layout, mode, out_dtype);
+  if (int st = check_out_dtype(E, out_dtype)) return st;
+  const int vec = P % 4 == 0 && aligned_to(coef, 16) && rgb_out_vec(out, out_dtype) ? 1 : 0;
+  const Enhance q = enhance_args(gain, kd, ks, spec_exp, lu, lv);
+  with_coef_dtype(coef_dtype, [&](auto c) {
+    with_layout(coef_layout, [&](auto cl) {
+      with_mode_out(mode, out_dtype, [&](auto m, auto t) {
+        lane4::launch(relight_enhanced_k<decltype(c), decltype(cl)::value, decltype(t), decltype(m)::value>, P,
+                      (hipStream_t)stream, coef, P, vec, q, out);
+      });
+    });
+  });
   return check_launch(E);
 }

@@ -11,7 +11,7 @@
 // three launches of, or the rti_rgb8 entry of the same coefficient values, bit for bit.
 //
 // The PTM-6 kernels keep rti_relight's lane map (a lane owns 4 consecutive pixels, a wave 256, a block 1024) and
-// rti_lrgb_px.h's loads: a full 256-pixel chunk of a pixel-major map reaches registers through 6 coalesced 1-KiB
+// rti_lane4.h's loads: a full 256-pixel chunk of a pixel-major map reaches registers through 6 coalesced 1-KiB
 // loads and the wave's LDS slab, one channel after the other through the same slab with wave-level fences only; a
 // planar map is read as 16-byte loads.  Three 4-byte output rows leave through the slab as whole 1-KiB stores,
 // uint8 rows as the lane's three dwords.  A launch whose P is no multiple of 4 or whose pointers or channel stride
@@ -29,9 +29,10 @@
 
 #include "rti_basis.h"
 #include "rti_convert.h"
+#include "rti_dispatch.h"
 #include "rti_enhance_px.h"
 #include "rti_hsh_px.h"
-#include "rti_lrgb_px.h"
+#include "rti_lane4.h"
 #include "rti_ptm_px.h"
 #include "rti_quant8.h"
 #include "rti_rgb_px.h"
@@ -40,9 +41,9 @@
 namespace rti {
 namespace {
 
-using namespace lrgb_px;  // K = 6, the wave loads of fp32 maps, the staged row stores
+using namespace lane4;  // the wave loads of fp32 maps and the sinks
+using rgb_px::K;        // PTM-6
 using hsh_px::dot_k;      // rti_relight's fp32 chain
-using quant8::store_dwords;
 using rgb_px::luminance;
 using rgb_px::normal_px;
 using rgb_px::Weights;
@@ -78,16 +79,6 @@ __device__ __forceinline__ void pixel_of(const float (&a)[3][4][K], int v, float
   for (int ch = 0; ch < 3; ++ch)
 #pragma unroll
     for (int j = 0; j < K; ++j) c[ch][j] = a[ch][v][j];
-}
-
-// the lane's four RGB pixels into the wave's 256 rows
-template <typename TO>
-__device__ __forceinline__ void store_rgb4(TO* __restrict__ rows, int lane, floatx4* __restrict__ slab,
-                                           const TO (&o)[4][3]) {
-  if constexpr (sizeof(TO) == 4)
-    store_rows_staged<3, TO>(rows, lane, slab, o);
-  else
-    store_dwords<12>(rows + 12 * lane, &o[0][0]);
 }
 
 template <typename TO, int CL>
@@ -316,7 +307,7 @@ relight_rgb_hsh_k(const float* __restrict__ coef, int64_t cs, int64_t P, int vin
   }
 }
 
-// ---- launchers and checks -----------------------------------------------------------------------------------------
+// ---- launchers --------------------------------------------------------------------------------------------------
 
 struct Maps {
   const float* coef;
@@ -325,44 +316,10 @@ struct Maps {
   hipStream_t s;
 };
 
-// f(layout tag): f is a generic lambda that launches the kernel instantiated on decltype of its argument
-template <int CL>
-struct LayoutTag {
-  static constexpr int value = CL;
-};
-
-template <typename F>
-inline void with_layout(int layout, F&& f) {
-  if (layout == RTI_COEF_PLANAR)
-    f(LayoutTag<RTI_COEF_PLANAR>{});
-  else
-    f(LayoutTag<RTI_COEF_PIXEL_MAJOR>{});
-}
-
-template <typename F>
-inline void with_out(int out_dtype, F&& f) {
-  switch (out_dtype) {
-    case RTI_F32: f(float{}); break;
-    case RTI_I32: f(int32_t{}); break;
-    default: f(uint8_t{}); break;
-  }
-}
-
 template <int KH, typename TO, int CL>
 void launch_hsh(const Maps& m, int vin, int vout, const double* luv, int E, void* out) {
   hipLaunchKernelGGL((relight_rgb_hsh_k<KH, TO, CL>), dim3(grid_1d(m.P, 256)), dim3(256), 0, m.s, m.coef, m.cs, m.P,
                      vin, vout, luv, E, static_cast<TO*>(out));
-}
-
-// P, the layout and the channel stride of three maps of k terms, in the order include/rti.h lists them
-int check_rgb_maps(const char* entry, int k, int layout, int64_t stride, int64_t P) {
-  if (int st = check_coef_layout(entry, layout)) return st;
-  return check_coef_stride(entry, coef_view(static_cast<const float*>(nullptr), layout, k, P, stride), P, 3);
-}
-
-// 16-byte loads of the three maps: every wave's rows (or plane pieces) of every channel start on a 16-byte boundary
-inline bool maps_vec(const float* coef, int64_t cs, int64_t P) {
-  return P % 4 == 0 && aligned_to(coef, 16) && cs % 4 == 0;
 }
 
 }  // namespace
@@ -378,18 +335,14 @@ extern "C" int rti_relight_rgb(const float* coef, int basis, int coef_layout, in
   const int k = basis_terms(basis);
   if (k < 0) return fail(RTI_ERR_BAD_ARG, "%s: unknown basis %d", E, basis);
   if (int st = check_rgb_maps(E, k, coef_layout, coef_channel_stride, P)) return st;
-  if (out_dtype != RTI_F32 && out_dtype != RTI_I32 && out_dtype != RTI_U8)
-    return fail(RTI_ERR_UNSUPPORTED, "%s: out dtype %d", E, out_dtype);
+  if (int st = check_out_dtype(E, out_dtype)) return st;
   const Maps m{coef, coef_layout, coef_channel_stride ? coef_channel_stride : P * k, P, (hipStream_t)stream};
   note_launches(1);
   if (k == K) {
-    const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // a lane's dword / the wave's 16-byte pieces
-    const int vec = maps_vec(coef, m.cs, P) && aligned_to(out, ovec) ? 1 : 0;
+    const int vec = maps_vec(coef, m.cs, P) && rgb_out_vec(out, out_dtype) ? 1 : 0;
     with_layout(coef_layout, [&](auto l) {
       with_out(out_dtype, [&](auto t) {
-        using TO = decltype(t);
-        hipLaunchKernelGGL((relight_rgb_ptm_k<TO, decltype(l)::value>), dim3(grid_1d(P, 1024)), dim3(256), 0, m.s,
-                           coef, m.cs, P, vec, luv, E_, static_cast<TO*>(out));
+        launch(relight_rgb_ptm_k<decltype(t), decltype(l)::value>, P, m.s, coef, m.cs, P, vec, luv, E_, out);
       });
     });
   } else {
@@ -420,17 +373,15 @@ extern "C" int rti_relight_rgb_enhanced(const float* coef, int coef_layout, int6
   if (int st = enhance_px::check_enhance(E, mode, gain, kd, ks, spec_exp, lu, lv)) return st;
   Weights wt;
   if (int st = rgb_px::host_weights(E, w, wt)) return st;
-  if (int st = enhance_px::check_enhance_out(E, out_dtype)) return st;
+  if (int st = check_out_dtype(E, out_dtype)) return st;
   const int64_t cs = coef_channel_stride ? coef_channel_stride : P * K;
-  const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // a lane's dword / the wave's 16-byte pieces
-  const int vec = maps_vec(coef, cs, P) && aligned_to(out, ovec) ? 1 : 0;
+  const int vec = maps_vec(coef, cs, P) && rgb_out_vec(out, out_dtype) ? 1 : 0;
   const enhance_px::Enhance q = enhance_px::enhance_args(gain, kd, ks, spec_exp, lu, lv);
   note_launches(1);
   with_layout(coef_layout, [&](auto l) {
     enhance_px::with_mode_out(mode, out_dtype, [&](auto m, auto t) {
-      using TO = decltype(t);
-      hipLaunchKernelGGL((relight_rgb_enhanced_k<TO, decltype(m)::value, decltype(l)::value>), dim3(grid_1d(P, 1024)),
-                         dim3(256), 0, (hipStream_t)stream, coef, cs, P, vec, wt, q, static_cast<TO*>(out));
+      launch(relight_rgb_enhanced_k<decltype(t), decltype(m)::value, decltype(l)::value>, P, (hipStream_t)stream, coef,
+             cs, P, vec, wt, q, out);
     });
   });
   return check_launch(E);
@@ -443,24 +394,17 @@ extern "C" int rti_rgb_normals(const float* coef, int coef_layout, int64_t coef_
   if (int st = check_pointers(E, {coef, normals})) return st;
   if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", E);
   if (int st = check_rgb_maps(E, K, coef_layout, coef_channel_stride, P)) return st;
-  if (normal_layout != RTI_NORMAL_PIXEL_MAJOR && normal_layout != RTI_NORMAL_PLANAR)
-    return fail(RTI_ERR_BAD_ARG, "%s: normal layout %d", E, normal_layout);
+  if (int st = check_normal_layout(E, normal_layout)) return st;
   Weights wt;
   if (int st = rgb_px::host_weights(E, w, wt)) return st;
   const int64_t cs = coef_channel_stride ? coef_channel_stride : P * K;
-  const int vec = maps_vec(coef, cs, P) && aligned_to(normals, 16) && (!kind || aligned_to(kind, 4)) &&
-                          (!peak || aligned_to(peak, 16))
-                      ? 1
-                      : 0;
+  const int vec = maps_vec(coef, cs, P) && normals_out_vec(normals, kind, peak) ? 1 : 0;
   note_launches(1);
   with_layout(coef_layout, [&](auto l) {
-    constexpr int CL = decltype(l)::value;
-    if (normal_layout == RTI_NORMAL_PLANAR)
-      hipLaunchKernelGGL((rgb_normals_k<RTI_NORMAL_PLANAR, CL>), dim3(grid_1d(P, 1024)), dim3(256), 0,
-                         (hipStream_t)stream, coef, cs, P, vec, wt, normals, kind, peak);
-    else
-      hipLaunchKernelGGL((rgb_normals_k<RTI_NORMAL_PIXEL_MAJOR, CL>), dim3(grid_1d(P, 1024)), dim3(256), 0,
-                         (hipStream_t)stream, coef, cs, P, vec, wt, normals, kind, peak);
+    with_normal_layout(normal_layout, [&](auto nl) {
+      launch(rgb_normals_k<decltype(nl)::value, decltype(l)::value>, P, (hipStream_t)stream, coef, cs, P, vec, wt,
+             normals, kind, peak);
+    });
   });
   return check_launch(E);
 }

@@ -19,7 +19,7 @@
 // no fp64 operation.  The table holds the very (float) values the expression gives, so nothing downstream can tell.
 //
 // All kernels keep rti_relight's lane map (a lane owns 4 consecutive pixels, a wave 256, a block 1024) and
-// rti_lrgb_px.h's loads of the fp32 maps.  A lane's 24 bytes of a channel block are contiguous: they are read as
+// rti_lane4.h's loads of the fp32 maps.  A lane's 24 bytes of a channel block are contiguous: they are read as
 // three 8-byte loads per block and written as six dwords.  The extremes pass is rti_quant8.h's, with a partial of 12
 // floats: the six minima and the six maxima over the three channels.
 //
@@ -33,9 +33,10 @@
 
 #include "rti_basis.h"
 #include "rti_convert.h"
+#include "rti_dispatch.h"
 #include "rti_enhance_px.h"
 #include "rti_hsh_px.h"
-#include "rti_lrgb_px.h"
+#include "rti_lane4.h"
 #include "rti_ptm_px.h"
 #include "rti_quant8.h"
 #include "rti_rgb_px.h"
@@ -44,7 +45,8 @@
 namespace rti {
 namespace {
 
-using namespace lrgb_px;  // K = 6, the wave loads of fp32 maps, the staged row stores
+using namespace lane4;  // the wave loads of fp32 maps, the byte source, the tables and the sinks
+using rgb_px::K;        // PTM-6
 using hsh_px::dot_k;      // rti_relight's fp32 chain
 using namespace quant8;
 using rgb_px::luminance;  // the fp32 luminance, its normal and the weights: shared with rti_rgb.hip
@@ -123,42 +125,7 @@ __device__ __forceinline__ void quantise_px(const float (&m)[K], const QParams<K
   }
 }
 
-// ---- dequantisation: six 256-entry tables per workgroup ---------------------------------------------------------
-// tab[j][t] = (float)(((double)t − bias_j)·scale_j), the fp32 value read_ptm gives byte t of plane j.  Every lane of
-// the workgroup's 256 forms entry t = threadIdx.x of the six tables; the caller synchronises the workgroup.
-
-constexpr int TAB = 256;
-
-__device__ __forceinline__ void fill_tables(const double* __restrict__ qparams, float* __restrict__ tab) {
-#pragma clang fp contract(off)
-  const double t = (double)threadIdx.x;
-#pragma unroll
-  for (int j = 0; j < K; ++j) tab[j * TAB + threadIdx.x] = (float)((t - qparams[K + j]) * qparams[j]);
-}
-
-// the 18 bytes of 4 consecutive pixels: three 8-byte loads from each of the three blocks
-struct Bytes4 {
-  union {
-    u32x2 v[3];
-    uint8_t b[4][K];
-  } c[3];
-};
-
-__device__ __forceinline__ void load_bytes4(const uint8_t* __restrict__ coef8, int64_t P, int64_t p0, Bytes4& r) {
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    const u32x2* s = reinterpret_cast<const u32x2*>(coef8 + ((int64_t)ch * P + p0) * K);
-#pragma unroll
-    for (int w = 0; w < 3; ++w) r.c[ch].v[w] = s[w];
-  }
-}
-
-__device__ __forceinline__ void load_bytes1(const uint8_t* __restrict__ coef8, int64_t P, int64_t p, uint8_t (&b)[3][K]) {
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch)
-#pragma unroll
-    for (int j = 0; j < K; ++j) b[ch][j] = coef8[((int64_t)ch * P + p) * K + j];
-}
+// ---- dequantisation: six 256-entry tables per workgroup (rti_lane4.h: fill_tables<6>, Rgb8Px, load_bytes) -------
 
 __device__ __forceinline__ void dequantise_px(const uint8_t (&b)[K], const float* __restrict__ tab, float (&a)[K]) {
 #pragma unroll
@@ -217,18 +184,17 @@ template <typename TO>
 __global__ void __launch_bounds__(256)
 relight_rgb8_k(const uint8_t* __restrict__ coef8, int64_t P, int vec, const double* __restrict__ qparams,
                const double* __restrict__ luv, int E, TO* __restrict__ out) {
-  constexpr bool STAGE_OUT = sizeof(TO) == 4;  // fp32 / int32: 48 B per lane through the slab
-  constexpr int SLAB = slab_v4(0, STAGE_OUT ? 3 : 0);
+  constexpr int SLAB = slab_v4(0, rgb_staged<TO>() ? 3 : 0);
   __shared__ floatx4 slabs[4 * SLAB];
   __shared__ float tab[K * TAB];
-  fill_tables(qparams, tab);
+  fill_tables<K>(qparams, tab);
   __syncthreads();  // the one workgroup barrier: waves may leave below
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
   if (wave_px >= P) return;
   floatx4* slab = slabs + wave * SLAB;
   if (vec && wave_px + 256 <= P) {  // wave-uniform
-    Bytes4 r;
+    Rgb8Px r;
     load_bytes4(coef8, P, wave_px + 4 * lane, r);
     float a[4][3][K];
 #pragma unroll
@@ -242,10 +208,7 @@ relight_rgb8_k(const uint8_t* __restrict__ coef8, int64_t P, int vec, const doub
 #pragma unroll
       for (int v = 0; v < 4; ++v) rgb_px<TO>(a[v], b, o[v]);
       TO* rows = out + ((int64_t)e * P + wave_px) * 3;
-      if constexpr (STAGE_OUT)
-        store_rows_staged<3, TO>(rows, lane, slab, o);
-      else
-        store_dwords<12>(rows + 12 * lane, &o[0][0]);
+      store_rgb4<TO>(rows, lane, slab, o);
     }
     return;
   }
@@ -277,7 +240,7 @@ rgb8_normals_k(const uint8_t* __restrict__ coef8, int64_t P, int vec, const doub
   constexpr int SLAB = slab_v4(0, STAGE_OUT ? 3 : 0);
   __shared__ floatx4 slabs[4 * SLAB];
   __shared__ float tab[K * TAB];
-  fill_tables(qparams, tab);
+  fill_tables<K>(qparams, tab);
   __syncthreads();  // the one workgroup barrier: waves may leave below
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
@@ -285,7 +248,7 @@ rgb8_normals_k(const uint8_t* __restrict__ coef8, int64_t P, int vec, const doub
   floatx4* slab = slabs + wave * SLAB;
   if (vec && wave_px + 256 <= P) {  // wave-uniform
     const int64_t p0 = wave_px + 4 * lane;
-    Bytes4 r;
+    Rgb8Px r;
     load_bytes4(coef8, P, p0, r);
     ptm_px::NormalOut o[4];
 #pragma unroll
@@ -335,18 +298,17 @@ template <typename TO, int MODE>
 __global__ void __launch_bounds__(256)
 relight_rgb8_enhanced_k(const uint8_t* __restrict__ coef8, int64_t P, int vec, const double* __restrict__ qparams,
                         Weights w, enhance_px::Enhance q, TO* __restrict__ out) {
-  constexpr bool STAGE_OUT = sizeof(TO) == 4;  // fp32 / int32: 48 B per lane through the slab
-  constexpr int SLAB = slab_v4(0, STAGE_OUT ? 3 : 0);
+  constexpr int SLAB = slab_v4(0, rgb_staged<TO>() ? 3 : 0);
   __shared__ floatx4 slabs[4 * SLAB];
   __shared__ float tab[K * TAB];
-  fill_tables(qparams, tab);
+  fill_tables<K>(qparams, tab);
   __syncthreads();  // the one workgroup barrier: waves may leave below
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 256;
   if (wave_px >= P) return;
   floatx4* slab = slabs + wave * SLAB;
   if (vec && wave_px + 256 <= P) {  // wave-uniform
-    Bytes4 r;
+    Rgb8Px r;
     load_bytes4(coef8, P, wave_px + 4 * lane, r);
     TO o[4][3];
 #pragma unroll
@@ -358,10 +320,7 @@ relight_rgb8_enhanced_k(const uint8_t* __restrict__ coef8, int64_t P, int vec, c
       enhance_px::rgb_enhanced<MODE, TO>(c, l, q, o[v]);
     }
     TO* rows = out + wave_px * 3;
-    if constexpr (STAGE_OUT)
-      store_rows_staged<3, TO>(rows, lane, slab, o);
-    else
-      store_dwords<12>(rows + 12 * lane, &o[0][0]);
+    store_rgb4<TO>(rows, lane, slab, o);
     return;
   }
   for (int j = 0; j < 4; ++j) {
@@ -380,27 +339,6 @@ relight_rgb8_enhanced_k(const uint8_t* __restrict__ coef8, int64_t P, int vec, c
   }
 }
 
-// ---- launchers and checks -----------------------------------------------------------------------------------------
-
-template <typename TO>
-void launch_relight8(const uint8_t* coef8, int64_t P, int vec, const double* qparams, const double* luv, int E,
-                     void* out, hipStream_t s) {
-  hipLaunchKernelGGL((relight_rgb8_k<TO>), dim3(grid_1d(P, 1024)), dim3(256), 0, s, coef8, P, vec, qparams, luv, E,
-                     static_cast<TO*>(out));
-}
-
-// the checks rti_rgb8_qparams and rti_rgb8_quantise share, in the order include/rti.h lists them
-int check_rgb_maps(const char* entry, int layout, int64_t stride, int64_t P) {
-  if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", entry);
-  if (int st = check_coef_layout(entry, layout)) return st;
-  return check_coef_stride(entry, coef_view(static_cast<const float*>(nullptr), layout, K, P, stride), P, 3);
-}
-
-// 16-byte loads of the three maps: every wave's rows (or plane pieces) of every channel start on a 16-byte boundary
-inline int maps_vec(const float* coef, int64_t cs, int64_t P) {
-  return P % 4 == 0 && aligned_to(coef, 16) && cs % 4 == 0 ? 1 : 0;
-}
-
 }  // namespace
 }  // namespace rti
 
@@ -414,20 +352,19 @@ extern "C" int rti_rgb8_qparams(const float* coef, int coef_layout, int64_t coef
                                 void* workspace, double* qparams, rti_stream_t stream) {
   const char* const E = "rti_rgb8_qparams";
   if (int st = check_pointers(E, {coef, workspace, qparams})) return st;
-  if (int st = check_rgb_maps(E, coef_layout, coef_channel_stride, P)) return st;
+  if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", E);
+  if (int st = check_rgb_maps(E, K, coef_layout, coef_channel_stride, P)) return st;
   if (!aligned_to(workspace, 4) || !aligned_to(qparams, 8))
     return fail(RTI_ERR_BAD_ARG, "%s: workspace must be 4-byte and qparams 8-byte aligned", E);
   const int64_t cs = coef_channel_stride ? coef_channel_stride : P * K;
   const int blocks = (int)qparams_blocks(P, 1024);
-  const int vec = maps_vec(coef, cs, P);
+  const int vec = maps_vec(coef, cs, P) ? 1 : 0;
   float* partial = static_cast<float*>(workspace);
   note_launches(2);
-  if (coef_layout == RTI_COEF_PLANAR)
-    hipLaunchKernelGGL((rgb_extremes_k<RTI_COEF_PLANAR>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, coef, cs, P,
-                       vec, partial);
-  else
-    hipLaunchKernelGGL((rgb_extremes_k<RTI_COEF_PIXEL_MAJOR>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, coef,
-                       cs, P, vec, partial);
+  with_layout(coef_layout, [&](auto cl) {
+    hipLaunchKernelGGL((rgb_extremes_k<decltype(cl)::value>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, coef, cs,
+                       P, vec, partial);
+  });
   if (int st = check_launch(E)) return st;
   hipLaunchKernelGGL(rgb_qparams_k, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, blocks, qparams);
   return check_launch(E);
@@ -437,17 +374,15 @@ extern "C" int rti_rgb8_quantise(const float* coef, int coef_layout, int64_t coe
                                  const double* qparams, uint8_t* coef8, rti_stream_t stream) {
   const char* const E = "rti_rgb8_quantise";
   if (int st = check_pointers(E, {coef, qparams, coef8})) return st;
-  if (int st = check_rgb_maps(E, coef_layout, coef_channel_stride, P)) return st;
-  if (!aligned_to(qparams, 8)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 8-byte aligned", E);
+  if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", E);
+  if (int st = check_rgb_maps(E, K, coef_layout, coef_channel_stride, P)) return st;
+  if (int st = check_qparams_aligned(E, qparams)) return st;
   const int64_t cs = coef_channel_stride ? coef_channel_stride : P * K;
   const int vec = maps_vec(coef, cs, P) && aligned_to(coef8, 8) ? 1 : 0;
   note_launches(1);
-  if (coef_layout == RTI_COEF_PLANAR)
-    hipLaunchKernelGGL((rgb_quantise_k<RTI_COEF_PLANAR>), dim3(grid_1d(P, 1024)), dim3(256), 0, (hipStream_t)stream,
-                       coef, cs, P, vec, qparams, coef8);
-  else
-    hipLaunchKernelGGL((rgb_quantise_k<RTI_COEF_PIXEL_MAJOR>), dim3(grid_1d(P, 1024)), dim3(256), 0,
-                       (hipStream_t)stream, coef, cs, P, vec, qparams, coef8);
+  with_layout(coef_layout, [&](auto cl) {
+    launch(rgb_quantise_k<decltype(cl)::value>, P, (hipStream_t)stream, coef, cs, P, vec, qparams, coef8);
+  });
   return check_launch(E);
 }
 
@@ -456,17 +391,13 @@ extern "C" int rti_relight_rgb8(const uint8_t* coef8, int64_t P, const double* q
   const char* const E = "rti_relight_rgb8";
   if (int st = check_pointers(E, {coef8, qparams, luv, out})) return st;
   if (P < 1 || E_ < 1) return fail(RTI_ERR_BAD_ARG, "%s: P and E must be positive", E);
-  if (out_dtype != RTI_F32 && out_dtype != RTI_I32 && out_dtype != RTI_U8)
-    return fail(RTI_ERR_UNSUPPORTED, "%s: out dtype %d", E, out_dtype);
-  if (!aligned_to(qparams, 8)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 8-byte aligned", E);
-  const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // a lane's dword / the wave's 16-byte pieces
-  const int vec = P % 4 == 0 && aligned_to(coef8, 8) && aligned_to(out, ovec) ? 1 : 0;
+  if (int st = check_out_dtype(E, out_dtype)) return st;
+  if (int st = check_qparams_aligned(E, qparams)) return st;
+  const int vec = P % 4 == 0 && aligned_to(coef8, 8) && rgb_out_vec(out, out_dtype) ? 1 : 0;
   note_launches(1);
-  switch (out_dtype) {
-    case RTI_F32: launch_relight8<float>(coef8, P, vec, qparams, luv, E_, out, (hipStream_t)stream); break;
-    case RTI_I32: launch_relight8<int32_t>(coef8, P, vec, qparams, luv, E_, out, (hipStream_t)stream); break;
-    default: launch_relight8<uint8_t>(coef8, P, vec, qparams, luv, E_, out, (hipStream_t)stream); break;
-  }
+  with_out(out_dtype, [&](auto t) {
+    launch(relight_rgb8_k<decltype(t)>, P, (hipStream_t)stream, coef8, P, vec, qparams, luv, E_, out);
+  });
   return check_launch(E);
 }
 
@@ -475,22 +406,15 @@ extern "C" int rti_rgb8_normals(const uint8_t* coef8, int64_t P, const double* q
   const char* const E = "rti_rgb8_normals";
   if (int st = check_pointers(E, {coef8, qparams, normals})) return st;
   if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", E);
-  if (normal_layout != RTI_NORMAL_PIXEL_MAJOR && normal_layout != RTI_NORMAL_PLANAR)
-    return fail(RTI_ERR_BAD_ARG, "%s: normal layout %d", E, normal_layout);
+  if (int st = check_normal_layout(E, normal_layout)) return st;
   Weights wt;
   if (int st = rgb_px::host_weights(E, w, wt)) return st;
-  if (!aligned_to(qparams, 8)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 8-byte aligned", E);
-  const int vec = P % 4 == 0 && aligned_to(coef8, 8) && aligned_to(normals, 16) && (!kind || aligned_to(kind, 4)) &&
-                          (!peak || aligned_to(peak, 16))
-                      ? 1
-                      : 0;
+  if (int st = check_qparams_aligned(E, qparams)) return st;
+  const int vec = P % 4 == 0 && aligned_to(coef8, 8) && normals_out_vec(normals, kind, peak) ? 1 : 0;
   note_launches(1);
-  if (normal_layout == RTI_NORMAL_PLANAR)
-    hipLaunchKernelGGL((rgb8_normals_k<RTI_NORMAL_PLANAR>), dim3(grid_1d(P, 1024)), dim3(256), 0, (hipStream_t)stream,
-                       coef8, P, vec, qparams, wt, normals, kind, peak);
-  else
-    hipLaunchKernelGGL((rgb8_normals_k<RTI_NORMAL_PIXEL_MAJOR>), dim3(grid_1d(P, 1024)), dim3(256), 0,
-                       (hipStream_t)stream, coef8, P, vec, qparams, wt, normals, kind, peak);
+  with_normal_layout(normal_layout, [&](auto nl) {
+    launch(rgb8_normals_k<decltype(nl)::value>, P, (hipStream_t)stream, coef8, P, vec, qparams, wt, normals, kind, peak);
+  });
   return check_launch(E);
 }
 
@@ -503,16 +427,14 @@ extern "C" int rti_relight_rgb8_enhanced(const uint8_t* coef8, int64_t P, const 
   if (int st = enhance_px::check_enhance(E, mode, gain, kd, ks, spec_exp, lu, lv)) return st;
   Weights wt;
   if (int st = rgb_px::host_weights(E, w, wt)) return st;
-  if (int st = enhance_px::check_enhance_out(E, out_dtype)) return st;
-  if (!aligned_to(qparams, 8)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 8-byte aligned", E);
-  const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // a lane's dword / the wave's 16-byte pieces
-  const int vec = P % 4 == 0 && aligned_to(coef8, 8) && aligned_to(out, ovec) ? 1 : 0;
+  if (int st = check_out_dtype(E, out_dtype)) return st;
+  if (int st = check_qparams_aligned(E, qparams)) return st;
+  const int vec = P % 4 == 0 && aligned_to(coef8, 8) && rgb_out_vec(out, out_dtype) ? 1 : 0;
   const enhance_px::Enhance q = enhance_px::enhance_args(gain, kd, ks, spec_exp, lu, lv);
   note_launches(1);
   enhance_px::with_mode_out(mode, out_dtype, [&](auto m, auto t) {
-    using TO = decltype(t);
-    hipLaunchKernelGGL((relight_rgb8_enhanced_k<TO, decltype(m)::value>), dim3(grid_1d(P, 1024)), dim3(256), 0,
-                       (hipStream_t)stream, coef8, P, vec, qparams, wt, q, static_cast<TO*>(out));
+    launch(relight_rgb8_enhanced_k<decltype(t), decltype(m)::value>, P, (hipStream_t)stream, coef8, P, vec, qparams,
+           wt, q, out);
   });
   return check_launch(E);
 }

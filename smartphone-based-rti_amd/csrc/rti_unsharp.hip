@@ -33,8 +33,9 @@
 #include <cstdint>
 
 #include "rti_convert.h"
+#include "rti_dispatch.h"
+#include "rti_lane4.h"
 #include "rti_shade.h"
-#include "rti_stack.h"
 
 namespace rti {
 namespace {
@@ -411,23 +412,6 @@ shade_normals_k(const float* __restrict__ normals, const float* __restrict__ alb
   }
 }
 
-template <int NL, typename TO>
-void launch_shade_t(const float* normals, const float* albedo, int64_t P, int vec, const Shade& q, void* out,
-                    hipStream_t s) {
-  hipLaunchKernelGGL((shade_normals_k<NL, TO>), dim3(grid_1d(P, 1024)), dim3(256), 0, s, normals, albedo, P, vec, q,
-                     static_cast<TO*>(out));
-}
-
-template <int NL>
-void launch_shade_out(const float* normals, const float* albedo, int64_t P, int vec, const Shade& q, void* out,
-                      int odt, hipStream_t s) {
-  switch (odt) {
-    case RTI_F32: launch_shade_t<NL, float>(normals, albedo, P, vec, q, out, s); break;
-    case RTI_I32: launch_shade_t<NL, int32_t>(normals, albedo, P, vec, q, out, s); break;
-    default: launch_shade_t<NL, uint8_t>(normals, albedo, P, vec, q, out, s); break;
-  }
-}
-
 bool sigma_ok(double sigma) { return std::isfinite(sigma) && sigma > 0.0; }
 
 }  // namespace
@@ -499,21 +483,20 @@ extern "C" int rti_shade_normals(const float* normals, int normal_layout, const 
   const char* const E = "rti_shade_normals";
   if (int st = check_pointers(E, {normals, out})) return st;
   if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", E);
-  if (normal_layout != RTI_NORMAL_PIXEL_MAJOR && normal_layout != RTI_NORMAL_PLANAR)
-    return fail(RTI_ERR_BAD_ARG, "%s: normal layout %d", E, normal_layout);
+  if (int st = check_normal_layout(E, normal_layout)) return st;
   if (!std::isfinite(lu) || !std::isfinite(lv)) return fail(RTI_ERR_BAD_ARG, "%s: non-finite light direction", E);
   if (!std::isfinite(kd) || !std::isfinite(ks)) return fail(RTI_ERR_BAD_ARG, "%s: non-finite kd or ks", E);
   if (spec_exp < 1 || spec_exp > 255) return fail(RTI_ERR_BAD_ARG, "%s: spec_exp %d outside [1, 255]", E, spec_exp);
-  if (out_dtype != RTI_F32 && out_dtype != RTI_I32 && out_dtype != RTI_U8)
-    return fail(RTI_ERR_UNSUPPORTED, "%s: out dtype %d", E, out_dtype);
+  if (int st = check_out_dtype(E, out_dtype)) return st;
   const LightFrame f = light_frame(lu, lv);
-  const size_t ovec = out_dtype == RTI_U8 ? 4 : 16;  // bytes of a lane's 4 outputs
-  const int vec = P % 4 == 0 && aligned_to(normals, 16) && (!albedo || aligned_to(albedo, 16)) && aligned_to(out, ovec);
+  const int vec =
+      P % 4 == 0 && aligned_to(normals, 16) && (!albedo || aligned_to(albedo, 16)) && rgb_out_vec(out, out_dtype);
   const Shade q{kd, ks, spec_exp, f.lu, f.lv, f.lw, f.hx, f.hy, f.hz};
-  hipStream_t s = (hipStream_t)stream;
-  if (normal_layout == RTI_NORMAL_PLANAR)
-    launch_shade_out<RTI_NORMAL_PLANAR>(normals, albedo, P, vec, q, out, out_dtype, s);
-  else
-    launch_shade_out<RTI_NORMAL_PIXEL_MAJOR>(normals, albedo, P, vec, q, out, out_dtype, s);
+  with_normal_layout(normal_layout, [&](auto nl) {
+    with_out(out_dtype, [&](auto t) {
+      lane4::launch(shade_normals_k<decltype(nl)::value, decltype(t)>, P, (hipStream_t)stream, normals, albedo, P, vec,
+                    q, out);
+    });
+  });
   return check_launch(E);
 }
