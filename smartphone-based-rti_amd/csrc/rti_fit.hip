@@ -379,9 +379,12 @@ fit_shared_mfma(const float* __restrict__ pinv, int k, int N, const T* __restric
     float x[S][4];
 #pragma unroll
     for (int s = 0; s < S; ++s) {
-      int n = n0 + 4 * s + r;
-      n = n < N ? n : N - 1;  // the padded rows of A are zero
-      load_px<T, 4, NT>(src + (int64_t)n * lstride, x[s]);
+      const int n = n0 + 4 * s + r;
+      // a padded light re-reads plane N - 1 (the load stays unconditional) and contributes a zero B operand:
+      // its zero row of A alone would turn an Inf or NaN of that plane into 0 · Inf = NaN
+      load_px<T, 4, NT>(src + (int64_t)(n < N ? n : N - 1) * lstride, x[s]);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) x[s][c] = n < N ? x[s][c] : 0.f;
     }
 #pragma unroll
     for (int s = 0; s < S; ++s) {
@@ -393,10 +396,11 @@ fit_shared_mfma(const float* __restrict__ pinv, int k, int N, const T* __restric
     }
   }
   for (; n0 < Npad; n0 += 4) {
-    int n = n0 + r;
-    n = n < N ? n : N - 1;
+    const int n = n0 + r;
     float x[4];
-    load_px<T, 4, NT>(src + (int64_t)n * lstride, x);
+    load_px<T, 4, NT>(src + (int64_t)(n < N ? n : N - 1) * lstride, x);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) x[c] = n < N ? x[c] : 0.f;
     const float a = a_col[n0 * 16];
     acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, x[0], acc0, 0, 0, 0);
     acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a, x[1], acc1, 0, 0, 0);
@@ -836,8 +840,8 @@ fit_shared_tile_s(const float* __restrict__ pinv, int k, int N, const T* __restr
 // hop, 1 KiB per wave instruction) into a ring of NB tiles, NB - 1 steps in flight.  A step
 // waits for its own wave's DMAs with a counted vmcnt and one raw s_barrier publishes it to the
 // workgroup (a __syncthreads() would drain every DMA in flight).  Lights past N re-read plane
-// N - 1 (their weights are zero) and lanes past the image re-read its last 4 pixels (never
-// stored), so every DMA is unconditional.
+// N - 1 (their B operands are zeroed when they are read back from LDS, as their weights are) and
+// lanes past the image re-read its last 4 pixels (never stored), so every DMA is unconditional.
 // one global_load_lds_dwordx4: lane i's 16 bytes land at lds + 16·i (lds wave-uniform)
 template <bool NT>
 __device__ __forceinline__ void glds16(const float* g, float* lds) {
@@ -911,9 +915,11 @@ fit_shared_tile_dma(const float* __restrict__ pinv, int k, int N, const float* _
 #pragma unroll
     for (int s = 0; s < SP; ++s) {
       const float a = lds_pinv[(t * S + 4 * s + r) * 16 + q];
+      const bool pad = t * S + 4 * s + r >= N;  // a padded light of the last step: plane N - 1 again
 #pragma unroll
       for (int g = 0; g < RC; ++g) {
-        const floatx4 x = *reinterpret_cast<const floatx4*>(tb + (4 * s + r) * R + pw + 64 * g + 4 * q);
+        floatx4 x = *reinterpret_cast<const floatx4*>(tb + (4 * s + r) * R + pw + 64 * g + 4 * q);
+        if (pad) x = floatx4{0.f, 0.f, 0.f, 0.f};  // not 0 · (an Inf or NaN of plane N - 1)
 #pragma unroll
         for (int c = 0; c < 4; ++c) acc[g][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, x[c], acc[g][c], 0, 0, 0);
       }
