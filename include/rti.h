@@ -299,6 +299,55 @@ int rti_fit_shared_robust(const double* A, int k, int N, const void* I, int in_d
                           float* res, int32_t* kept, int* fallback_px, int kernel, rti_stream_t stream);
 int rti_fit_shared_robust_plan(int k, int N, int in_dtype, int iters, int kernel);
 
+/* ---- device: photometric stereo (rti_ps.hip) -------------------------------------------
+ * Robust Lambertian normals and albedo fitted to the stack itself: I_n = g·l_n per pixel with the
+ * samples the model cannot describe (attached shadow, clipped highlight) left out, n = g/|g| and albedo
+ * |g|: the normal map of RTIBuilder and Relight.  (rti_ptm_normals and rti_hsh_normals read a normal off a
+ * fitted function and inherit what shadows and highlights did to that fit.)
+ *
+ * rti_ps_design (host): A[n][3] = (lu, lv, lw), lw = sqrt(max(0, 1 − lu² − lv²)) formed in fp64 from the
+ * fp32 inputs; a caller with measured lz writes its own third column.  RTI_ERR_BAD_ARG: a null pointer, n < 1.
+ *
+ * rti_photometric_stereo: per channel c and pixel p the fit is rti_fit_shared_robust's, word for word, at
+ * k = 3 (window compared on the input value, solve(w) with the same Cholesky and pivot rule, fallback to
+ * every light, Huber IRLS; res, kept and fallback_px, one count per channel-pixel that fell back, as there).
+ * It gives g_c in fp64.  Then, in fp64 without contraction, in the written order:
+ *   g      = g_0 (C = 1);  g_j = fma(w_2, g_2j, fma(w_1, g_1j, w_0·g_0j)) (C = 3)
+ *   s      = sqrt(g_x² + g_y² + g_z²),  n = g/s
+ *   albedo_c = g_c·n, an fma chain over x, y, z starting from 0
+ *   kind 0  s > 0 and g_z >= 0
+ *   kind 1  s > 0 and g_z < 0: the normal is returned as fitted, not clamped
+ *   kind 2  s == 0: n = (0, 0, 1), albedo as defined (0 for C = 1)
+ *   kind 4  a non-finite component of any g_c: n and every albedo are NaN; res and kept are what the fit
+ *           produced                                              (3 is not used: rti_ptm_normals' numbers)
+ * and every output is rounded once to fp32.
+ * A: device fp64 [N][3].  I, in_dtype (F32 / U8 / I32), P and the strides as rti_fit_shared (light-major);
+ * C = 1 (grey) or 3 (RGB: one normal per pixel from all three channels).  w: HOST [3], NULL = 0.299, 0.587,
+ * 0.114; read only when C == 3.  normals: device fp32, normal_layout as rti_ptm_normals; albedo: device fp32
+ * [C][P]; kind: uint8 [P] or NULL; res: fp32 [C][P] or NULL; kept: int32 [C][P] or NULL; fallback_px: NULL or
+ * a device int the caller zeroes.
+ * Every argument check answers before any HIP call.  RTI_ERR_BAD_ARG: null A / I / normals / albedo; N < 3;
+ * P < 1; lo > hi or a NaN bound; min_lights outside [3, N]; iters outside [0, 16]; delta <= 0 or NaN with
+ * iters > 0; a bad normal layout; a non-finite weight; a non-zero light_stride < P; with C = 3 a non-zero
+ * channel stride below its dense value; any kernel bit but RTI_KERNEL_ONE_LAUNCH.  RTI_ERR_UNSUPPORTED: C
+ * outside {1, 3}; an in_dtype other than F32 / U8 / I32.
+ * One launch; one lane owns one pixel with all its channels.  Forms (the same arithmetic in the same order,
+ * hence the same bits): STREAMING reads the samples from global memory in every pass (iters == 0: the stack
+ * once, the residual energy from q − 2cᵀb + cᵀGc; also when no tile fits, or with RTI_KERNEL_ONE_LAUNCH).
+ * RESIDENT (iters > 0) copies a workgroup's tile [C][N][TP] into LDS once, by 16-byte loads when every plane
+ * of the tile is 16-byte aligned; TP = the largest of 256 / 128 / 64 with C·N·TP·sizeof(element) <= 160 KiB.
+ * rti_photometric_stereo_plan returns TP, or 0 for the streaming form.
+ * Not built: pixel-major stacks, per-pixel light directions, fp64 stacks, a chunked (FitAccumulator) form
+ * (the window needs the samples), a multi-GPU split. */
+int rti_ps_design(const float* lu, const float* lv, int n, double* A);
+int rti_photometric_stereo_plan(int N, int in_dtype, int C, int iters, int kernel);
+int rti_photometric_stereo(const double* A, int N, const void* I, int in_dtype, int64_t P, int C,
+                           int64_t light_stride, int64_t channel_stride,
+                           float lo, float hi, int min_lights, int iters, float delta,
+                           const float* w, float* normals, int normal_layout, float* albedo,
+                           uint8_t* kind, float* res, int32_t* kept, int* fallback_px,
+                           int kernel, rti_stream_t stream);
+
 /* ---- device: the shared fit fed in chunks of light planes (rti_fit_accum.hip) -----------
  * rti_fit_shared_residual's per-pixel sums kept in HBM between calls, for stacks that do not fit beside
  * their outputs and for frames that arrive over time (analysis.py produces one intensity plane and one

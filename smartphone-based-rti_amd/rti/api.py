@@ -653,6 +653,109 @@ def fit_robust(I, lu, lv, basis="ptm", *, lo=None, hi=None, min_lights=None, ite
     return _unflatten(coef, spatial, lead, cl), _unflatten(res, spatial, lead), _unflatten(kept, spatial, lead)
 
 
+def ps_design(lu, lv, lz=None):
+    """Host fp64 design matrix [N, 3] of photometric stereo (``rti_ps_design``): the rows (lu, lv, lw) with
+    lw = sqrt(max(0, 1 − lu² − lv²)), or with a measured third component ``lz`` in its place."""
+    lu, lv = _dirs(lu, lv)
+    A = np.empty((lu.size, 3), dtype=np.float64)
+    L.check(L.lib().rti_ps_design(_fptr(lu), _fptr(lv), lu.size, _dptr(A)), "rti_ps_design")
+    if lz is not None:
+        lz = np.asarray(lz.detach().cpu() if torch.is_tensor(lz) else lz, dtype=np.float64).ravel()
+        if lz.size != lu.size:
+            raise ValueError("lz and lu differ in length")
+        A[:, 2] = lz
+    return A
+
+
+def photometric_stereo_into(A_dev, I3, normals, albedo, kind, res, kept, fallback, *, lo, hi, min_lights, iters=0,
+                            delta=0.0, weights=None, normal_layout="pixel", kernel=0, light_stride=None):
+    """Launch ``rti_photometric_stereo`` on preallocated tensors (no allocation, graph-capturable).
+
+    A_dev fp64 [N, 3] (``ps_design`` on the device), I3 CUDA [C, N, P] light-major (fp32/u8/int32), C = 1 or 3;
+    with ``light_stride`` > P it is a view of planes padded to that many elements (channel stride
+    N·light_stride).  normals fp32 [P, 3] (normal_layout="pixel") or [3, P], albedo fp32 [C, P], kind uint8 [P]
+    or None, res fp32 [C, P] or None, kept int32 [C, P] or None, fallback int32 [1] zeroed (or None): the count
+    of channel-pixels that fell back to every light.  lo / hi: the intensity window (±inf = no bound); weights:
+    None or the three luminance weights that combine an RGB pixel's channels into its normal; kernel: 0 or
+    ``RTI_KERNEL_ONE_LAUNCH`` (the streaming form, for measurement)."""
+    C, N, P = I3.shape
+    ls = P if light_stride is None else int(light_stride)
+    if A_dev.dtype != torch.float64 or tuple(A_dev.shape) != (N, 3) or not A_dev.is_contiguous():
+        raise ValueError(f"A must be contiguous float64 [{N}, 3]; got {A_dev.dtype} {tuple(A_dev.shape)}")
+    if ls < P or any(n > 1 and s != w for n, s, w in zip(I3.shape, I3.stride(), (N * ls, ls, 1))):
+        raise ValueError(f"I3 strides {tuple(I3.stride())} are not light-major planes of stride {ls}")
+
+    def opt(t, name, dtype, n):
+        return None if t is None else _map_out(t, name, dtype, n, I3)
+
+    st = L.lib().rti_photometric_stereo(_vp(A_dev), N, _vp(I3), _IN_DTYPES[I3.dtype], P, C, ls, N * ls, float(lo),
+                                        float(hi), int(min_lights), int(iters), float(delta), _luma_weights(weights),
+                                        _map_out(normals, "normals", torch.float32, 3 * P, I3),
+                                        _normal_layout_id(normal_layout),
+                                        _map_out(albedo, "albedo", torch.float32, C * P, I3),
+                                        opt(kind, "kind", torch.uint8, P), opt(res, "res", torch.float32, C * P),
+                                        opt(kept, "kept", torch.int32, C * P), opt(fallback, "fallback", torch.int32, 1),
+                                        int(kernel), _stream_of(I3))
+    L.check(st, "rti_photometric_stereo")
+
+
+def photometric_stereo(I, lu, lv, lz=None, *, lo=None, hi=None, min_lights=None, iters=0, delta=None, weights=None,
+                       normal_layout="pixel", return_kind=False, return_res=False, return_kept=False, stats=None,
+                       kernel=0):
+    """Surface normals and albedo by photometric stereo on the GPU (``rti_photometric_stereo``): the Lambertian
+    model I_n = g·l_n fitted per pixel to the stack itself, n = g/‖g‖ and albedo ‖g‖, the normal map of
+    RTIBuilder and Relight.  The samples the model cannot describe are left out as ``fit_robust`` leaves them
+    out: those outside the intensity window [lo, hi] (attached shadow, clipped highlight) are dropped and, with
+    iters > 0, the rest are reweighted ``iters`` times by Huber's function of their residuals (delta in
+    intensity units).
+
+    I: CUDA [N, P], [N, H, W] or [3, N, H, W] (light-major, fp32/u8/int32); an RGB stack gives ONE normal per
+    pixel, from the weighted sum of its channels' fits (weights, default 0.299, 0.587, 0.114), and an albedo per
+    channel.  lz: the lights' measured third component (default sqrt(1 − lu² − lv²)).  lo / hi: None = no bound;
+    a uint8 stack given NEITHER bound uses 1..254.  min_lights (default 3): a channel of a pixel with fewer
+    samples in the window, or whose windowed system is rank-deficient, falls back to every light.
+
+    Returns ``(normals, albedo)``: fp32 unit normals [H, W, 3] (or [3, H, W] with normal_layout="planar") and
+    fp32 albedo [H, W], or [H, W, 3] for RGB (an image).  Then, as asked: with return_kind uint8 [H, W] (0 a
+    normal facing the viewer, 1 one facing away, returned as fitted, 2 g = 0: (0, 0, 1), 4 non-finite: NaN);
+    with return_res fp32 [H, W] ([3, H, W] for RGB), the RMS residual over the window; with return_kept int32 of
+    that shape, the samples in the window (N after a fallback).  ``stats``, if a dict, receives ``fallback_px``
+    (this waits for the kernel)."""
+    _require_cuda(I, "I")
+    if I.dtype not in _IN_DTYPES:
+        raise ValueError(f"I dtype {I.dtype} unsupported (float32, uint8 or int32)")
+    nl = _normal_layout_id(normal_layout)
+    C, N, P, spatial = _stack_shape(I)
+    if C not in (1, 3):
+        raise ValueError(f"a 4-D stack must be RGB, [3, N, H, W]; got {C} channels")
+    if N < 3:
+        raise ValueError(f"shapes not aligned: {N} lights < 3 unknowns")
+    A = ps_design(lu, lv, lz)
+    if A.shape[0] != N:
+        raise ValueError(f"{A.shape[0]} light directions for {N} intensity planes")
+    lo, hi = _robust_window(I, lo, hi)
+    dev = I.device
+    lead = I.dim() == 4
+    normals = _coef_empty(1, P, 3, nl, torch.float32, dev)
+    albedo = torch.empty((C, P), dtype=torch.float32, device=dev)
+    kind = torch.empty((1, P), dtype=torch.uint8, device=dev) if return_kind else None
+    res = torch.empty((C, P), dtype=torch.float32, device=dev) if return_res else None
+    kept = torch.empty((C, P), dtype=torch.int32, device=dev) if return_kept else None
+    fallback = torch.zeros(1, dtype=torch.int32, device=dev) if isinstance(stats, dict) else None
+    photometric_stereo_into(torch.as_tensor(A, device=dev).contiguous(), _stack3(I, C, N, P), normals, albedo, kind,
+                            res, kept, fallback, lo=lo, hi=hi, min_lights=3 if min_lights is None else min_lights,
+                            iters=iters, delta=0.0 if delta is None else delta, weights=weights, normal_layout=nl,
+                            kernel=kernel)
+    if fallback is not None:
+        stats["fallback_px"] = int(fallback.item())
+    alb = _unflatten(albedo, spatial, lead)
+    out = [_unflatten(normals, spatial, False, nl), alb.movedim(0, -1).contiguous() if lead else alb]
+    if return_kind:
+        out.append(_unflatten(kind, spatial, False))
+    out += [_unflatten(t, spatial, lead) for t in (res, kept) if t is not None]
+    return tuple(out)
+
+
 def fit_accumulate_into(R_dev, I3, state, *, k, init=False, light_stride=None):
     """Launch ``rti_fit_accumulate`` on preallocated tensors (no allocation, graph-capturable): add the chunk's
     B light planes to the fit state.

@@ -1,6 +1,6 @@
 """PyTorch custom ops over the C ABI: ``torch.ops.rti.fit_shared`` / ``fit_shared_residual`` /
-``fit_robust`` / ``fit_accumulate`` / ``fit_accum_solve`` / ``fit_residual`` / ``relight`` / ``ptm_normals`` /
-``relight_enhanced`` / ``map_unsharp`` / ``shade_normals`` / ``lrgb_from_rgb`` / ``relight_lrgb`` /
+``fit_robust`` / ``photometric_stereo`` / ``fit_accumulate`` / ``fit_accum_solve`` / ``fit_residual`` / ``relight`` /
+``ptm_normals`` / ``relight_enhanced`` / ``map_unsharp`` / ``shade_normals`` / ``lrgb_from_rgb`` / ``relight_lrgb`` /
 ``lrgb_quantise`` / ``relight_lrgb8`` / ``hsh_quantise`` / ``relight_hsh8`` / ``hsh_normals`` / ``hsh8_normals`` /
 ``rgb8_quantise`` / ``relight_rgb8`` / ``rgb8_normals`` / ``relight_lrgb_enhanced`` / ``relight_lrgb8_enhanced`` /
 ``relight_rgb8_enhanced`` / ``relight_rgb`` / ``relight_rgb_enhanced`` / ``rgb_normals`` / ``relight_hsh_specular`` /
@@ -150,6 +150,45 @@ def fit_robust(A: torch.Tensor, I: torch.Tensor, lo: float, hi: float, min_light
 def _(A, I, lo, hi, min_lights, iters=0, delta=0.0, planar=False, kernel=0):
     return _outputs(I, _lead(I), I.shape[-1], A.shape[1], planar, (torch.float32, torch.int32)) + (
         I.new_empty((1,), dtype=torch.int32),)
+
+
+def _ps_outputs(I, lead, P, planar):
+    """photometric_stereo's outputs on I's device: normals [P, 3] (or [3, P] if planar), albedo lead + [P], kind
+    [P], res and kept lead + [P], fallback_px [1]; lead = (C,) or the caller's own."""
+    return (I.new_empty((3, P) if planar else (P, 3), dtype=torch.float32),
+            I.new_empty(lead + (P,), dtype=torch.float32), I.new_empty((P,), dtype=torch.uint8),
+            I.new_empty(lead + (P,), dtype=torch.float32), I.new_empty(lead + (P,), dtype=torch.int32),
+            I.new_zeros((1,), dtype=torch.int32))
+
+
+@torch.library.custom_op("rti::photometric_stereo", mutates_args=())
+def photometric_stereo(A: torch.Tensor, I: torch.Tensor, lo: float, hi: float, min_lights: int, iters: int = 0,
+                       delta: float = 0.0, weights: Optional[Sequence[float]] = None, planar: bool = False,
+                       kernel: int = 0) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
+                                                 torch.Tensor]:
+    """Photometric stereo (``rti_photometric_stereo``: the robust Lambertian fit with the intensity window
+    [lo, hi], ±inf = no bound, and ``iters`` Huber IRLS steps of width delta).  A fp64 CUDA [N, 3]
+    (``rti.ps_design``), I CUDA [N, P] or [3, N, P] (fp32/u8/int32) -> ``(normals, albedo, kind, res, kept,
+    fallback_px)``: normals fp32 [P, 3] (or [3, P] if planar), albedo fp32 [C?, P], kind uint8 [P], res fp32
+    [C?, P], kept int32 [C?, P], fallback_px int32 [1]."""
+    api._require_cuda(I, "I")
+    api._require_cuda(A, "A")
+    if A.dtype != torch.float64:
+        raise ValueError("A must be float64 (rti.ps_design)")
+    _same_device(A=A, I=I)
+    _in_dtype(I)
+    I3 = _batched(I)
+    C, N, P = I3.shape
+    normals, albedo, kind, res, kept, fallback = _ps_outputs(I, (C,), P, planar)
+    api.photometric_stereo_into(A.contiguous(), I3, normals, albedo, kind, res, kept, fallback, lo=lo, hi=hi,
+                                min_lights=min_lights, iters=iters, delta=delta, weights=weights,
+                                normal_layout="planar" if planar else "pixel", kernel=kernel)
+    return (normals,) + _unbatched(I, albedo) + (kind,) + _unbatched(I, res, kept) + (fallback,)
+
+
+@photometric_stereo.register_fake
+def _(A, I, lo, hi, min_lights, iters=0, delta=0.0, weights=None, planar=False, kernel=0):
+    return _ps_outputs(I, _lead(I), I.shape[-1], planar)
 
 
 def _accum_state(state, k):
