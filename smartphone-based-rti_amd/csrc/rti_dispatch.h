@@ -33,6 +33,24 @@ inline void with_normal_layout(int normal_layout, F&& f) {
     f(Tag<RTI_NORMAL_PIXEL_MAJOR>{});
 }
 
+// the terms of an HSH basis, 9 or 16 (after the entry's check of the basis)
+template <typename F>
+inline void with_hsh_terms(int k, F&& f) {
+  if (k == 9)
+    f(Tag<9>{});
+  else
+    f(Tag<16>{});
+}
+
+// one map or three (after the entry's check of C)
+template <typename F>
+inline void with_channels(int C, F&& f) {
+  if (C == 1)
+    f(Tag<1>{});
+  else
+    f(Tag<3>{});
+}
+
 // f(TO{}) with TO the output type (after check_out_dtype)
 template <typename F>
 inline void with_out(int out_dtype, F&& f) {

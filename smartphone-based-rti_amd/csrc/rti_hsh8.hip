@@ -15,7 +15,8 @@
 // are not dword-aligned): a lane then takes its 3k bytes out of the slab as dwords, realigned with a funnel
 // shift for k = 9.  fp32 rows of the pixel-major maps and the output rows go through the slab the same way.
 // Anything the pieces cannot serve (a pointer off its alignment, the last partial wave) loads and stores per
-// lane, through the same per-pixel functions.
+// lane, through the same per-pixel functions.  The two sources of a pixel are rti_hsh_px.h's, the store of a
+// direction's rows rti_hsh_render_px.h's.
 //
 // The extremes pass is rti_quant8.h's, with a partial of 2k floats: the k minima and the k maxima over the three
 // channels.  A zero minimum is stored as +0, so the bias does not depend on the order of the reduction either.
@@ -27,46 +28,19 @@
 
 #include "rti_basis.h"
 #include "rti_convert.h"
-#include "rti_hsh_px.h"
+#include "rti_dispatch.h"
+#include "rti_hsh_render_px.h"
 #include "rti_quant8.h"
 #include "rti_stack.h"
 
 namespace rti {
 namespace {
 
-using namespace hsh_px;  // the chain, the slab runs and the dequantisation, shared with rti_hsh_normals.hip
+using namespace hsh_px;  // the chain, the slab runs and the two sources of a pixel
 using namespace quant8;
 
 constexpr int ECH = 64;     // directions per basis table in LDS (rti_relight's)
 constexpr int CHUNK = 256;  // pixels of a workgroup
-
-// ---- the three fp32 maps of a pixel -----------------------------------------------------------------------------
-// x[c][j] of pixel wave_px + lane.  staged (wave-uniform; pixel-major, a full wave, 16-byte aligned rows): the
-// wave's 64 rows of a channel are one run.  Otherwise a live lane loads its own values (planar maps: coalesced
-// as they are) and a lane past the image gets NaNs, which the extremes skip.
-template <int K, int CL>
-__device__ __forceinline__ void load_px(const float* __restrict__ coef, int64_t cs, int64_t P, int64_t wave_px, int lane,
-                                        bool live, bool staged, u32x4* __restrict__ slab, float (&x)[3][K]) {
-  if constexpr (CL == RTI_COEF_PIXEL_MAJOR) {
-    if (staged) {
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        run_in<4 * K>(coef + c * cs + wave_px * K, lane, slab);
-        uint32_t w[K];
-        lane_words<4 * K>(slab, lane, w);
-#pragma unroll
-        for (int j = 0; j < K; ++j) x[c][j] = __uint_as_float(w[j]);
-      }
-      return;
-    }
-  }
-  const int64_t p = wave_px + lane;
-#pragma unroll
-  for (int c = 0; c < 3; ++c)
-#pragma unroll
-    for (int j = 0; j < K; ++j)
-      x[c][j] = !live ? NAN : CL == RTI_COEF_PLANAR ? coef[c * cs + (int64_t)j * P + p] : coef[c * cs + p * K + j];
-}
 
 // ---- extremes ----------------------------------------------------------------------------------------------------
 // q[j], q[K + j]: min and max of the finite values of term j in the three channels.
@@ -85,7 +59,9 @@ hsh_extremes_k(const float* __restrict__ coef, int64_t cs, int64_t P, int vin, f
     const int64_t wave_px = (c * 4 + wave) * 64;
     if (wave_px >= P) continue;  // wave-uniform
     float x[3][K];
-    load_px<K, CL>(coef, cs, P, wave_px, lane, wave_px + lane < P, vin && wave_px + 64 <= P, slabs + wave * SLAB, x);
+    // a lane past the image gets NaNs, which the extremes skip
+    load_px<K, 3, CL>(coef, cs, P, wave_px, lane, wave_px + lane < P, vin && wave_px + 64 <= P, NAN,
+                      slabs + wave * SLAB, x);
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch)
 #pragma unroll
@@ -153,7 +129,7 @@ hsh_quantise_k(const float* __restrict__ coef, int64_t cs, int64_t P, int vin, i
   const int64_t p = wave_px + lane;
   const bool live = p < P, full = wave_px + 64 <= P;
   float x[3][K];
-  load_px<K, CL>(coef, cs, P, wave_px, lane, live, vin && full, slab, x);
+  load_px<K, 3, CL>(coef, cs, P, wave_px, lane, live, vin && full, NAN, slab, x);
   uint32_t w[NW];
   quantise_px<K>(x, qs, w);
   if (vout && full) {  // wave-uniform
@@ -169,8 +145,7 @@ template <int K, typename TO>
 __global__ void __launch_bounds__(256)
 relight_hsh8_k(const uint8_t* __restrict__ coef8, int64_t P, int vin, int vout,
                const float* __restrict__ qparams, const double* __restrict__ luv, int E, TO* __restrict__ out) {
-  constexpr int NB = 3 * K, NW = (NB + 3) / 4;
-  constexpr int SLAB = slab_v4(run_v4<NB>(), run_v4<12>());  // bytes in; 64 rows of 3 elements of <= 4 bytes out
+  constexpr int SLAB = slab_v4(run_v4<3 * K>(), run_v4<12>());  // bytes in; 64 rows of 3 elements of <= 4 bytes out
   __shared__ u32x4 slabs[4 * SLAB];
   __shared__ float btab[ECH * K];
   __shared__ float qs[2 * K];
@@ -180,20 +155,9 @@ relight_hsh8_k(const uint8_t* __restrict__ coef8, int64_t P, int vin, int vout,
   __syncthreads();
   // every lane stays to the end: the basis tables are filled by the whole workgroup
   const int64_t wave_px = ((int64_t)blockIdx.x * 4 + wave) * 64;
-  const int64_t p = wave_px + lane;
-  const bool live = p < P, full = wave_px + 64 <= P;  // full: wave-uniform
-  uint32_t w[NW];
-#pragma unroll
-  for (int i = 0; i < NW; ++i) w[i] = 0;
-  if (vin && full) {
-    run_in<NB>(coef8 + wave_px * NB, lane, slab);
-    lane_words<NB>(slab, lane, w);
-  } else if (live) {
-#pragma unroll
-    for (int i = 0; i < NB; ++i) w[i >> 2] |= (uint32_t)coef8[p * NB + i] << (8 * (i & 3));
-  }
+  const bool live = wave_px + lane < P, full = wave_px + 64 <= P;  // full: wave-uniform
   float c[3][K];
-  dequantise_px<K>(w, qs, c);
+  load_px8<K>(coef8, wave_px, lane, live, vin && full, slab, qs, c);
 
   for (int e0 = 0; e0 < E; e0 += ECH) {
     const int ne = min(ECH, E - e0);
@@ -210,95 +174,8 @@ relight_hsh8_k(const uint8_t* __restrict__ coef8, int64_t P, int vin, int vout,
       TO o[3];
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) o[ch] = cvt_out<TO>(dot_k<K>(c[ch], b));
-      TO* rows = out + ((int64_t)(e0 + e) * P + wave_px) * 3;
-      if (vout && full) {  // wave-uniform: the wave's 192 elements as whole dwords
-        uint32_t* d = reinterpret_cast<uint32_t*>(rows);
-        const uint32_t* s = reinterpret_cast<const uint32_t*>(slab);
-        if constexpr (sizeof(TO) == 4) {
-          uint32_t* sw = reinterpret_cast<uint32_t*>(slab) + 3 * lane;
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) sw[ch] = __builtin_bit_cast(uint32_t, o[ch]);
-          wave_lds_sync();
-#pragma unroll
-          for (int j = 0; j < 3; ++j) d[j * 64 + lane] = s[j * 64 + lane];
-        } else {
-          uint8_t* sb = reinterpret_cast<uint8_t*>(slab) + 3 * lane;
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) sb[ch] = o[ch];
-          wave_lds_sync();
-          if (lane < 48) d[lane] = s[lane];
-        }
-        wave_lds_sync();  // the slab may be written again
-      } else if (live) {
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) rows[3 * lane + ch] = o[ch];
-      }
+      hsh_render::store_dir<3, TO>(o, out + ((int64_t)(e0 + e) * P + wave_px) * 3, lane, live, vout && full, slab);
     }
-  }
-}
-
-struct HshArgs {
-  const float* coef;
-  int layout;
-  int64_t cs, P;
-  int vin;
-  hipStream_t s;
-};
-
-template <int K, int CL>
-void launch_extremes(const HshArgs& a, int blocks, float* partial) {
-  hipLaunchKernelGGL((hsh_extremes_k<K, CL>), dim3(blocks), dim3(256), 0, a.s, a.coef, a.cs, a.P, a.vin, partial);
-}
-
-template <int K, int CL>
-void launch_quantise(const HshArgs& a, int vout, const float* qparams, uint8_t* coef8) {
-  hipLaunchKernelGGL((hsh_quantise_k<K, CL>), dim3(grid_1d(a.P, CHUNK)), dim3(256), 0, a.s, a.coef, a.cs, a.P, a.vin,
-                     vout, qparams, coef8);
-}
-
-// f.template operator()<K, CL>() for the call's term count and layout
-template <typename F>
-void with_k_layout(int k, int layout, F&& f) {
-  if (k == 9) {
-    if (layout == RTI_COEF_PLANAR) f.template operator()<9, RTI_COEF_PLANAR>();
-    else f.template operator()<9, RTI_COEF_PIXEL_MAJOR>();
-  } else {
-    if (layout == RTI_COEF_PLANAR) f.template operator()<16, RTI_COEF_PLANAR>();
-    else f.template operator()<16, RTI_COEF_PIXEL_MAJOR>();
-  }
-}
-
-struct Extremes {
-  const HshArgs& a;
-  int blocks;
-  float* partial;
-  template <int K, int CL>
-  void operator()() const { launch_extremes<K, CL>(a, blocks, partial); }
-};
-
-struct Quantise {
-  const HshArgs& a;
-  int vout;
-  const float* qparams;
-  uint8_t* coef8;
-  template <int K, int CL>
-  void operator()() const { launch_quantise<K, CL>(a, vout, qparams, coef8); }
-};
-
-template <int K, typename TO>
-void launch_relight8(const uint8_t* coef8, int64_t P, int vin, int vout, const float* qparams,
-                     const double* luv, int E, void* out, hipStream_t s) {
-  hipLaunchKernelGGL((relight_hsh8_k<K, TO>), dim3(grid_1d(P, CHUNK)), dim3(256), 0, s, coef8, P, vin, vout,
-                     qparams, luv, E, static_cast<TO*>(out));
-}
-
-template <int K>
-void launch_relight8_out(int out_dtype, const uint8_t* coef8, int64_t P, int vin, int vout,
-                         const float* qparams, const double* luv, int E, void* out, hipStream_t s) {
-  switch (out_dtype) {
-    case RTI_F32: launch_relight8<K, float>(coef8, P, vin, vout, qparams, luv, E, out, s); break;
-    case RTI_I32: launch_relight8<K, int32_t>(coef8, P, vin, vout, qparams, luv, E, out, s); break;
-    default: launch_relight8<K, uint8_t>(coef8, P, vin, vout, qparams, luv, E, out, s); break;
   }
 }
 
@@ -306,14 +183,7 @@ void launch_relight8_out(int out_dtype, const uint8_t* coef8, int64_t P, int vin
 int check_hsh_maps(const char* entry, int basis, int layout, int64_t stride, int64_t P) {
   if (P < 1) return fail(RTI_ERR_BAD_ARG, "%s: P must be positive", entry);
   if (!hsh_basis(basis)) return fail(RTI_ERR_UNSUPPORTED, "%s: basis %d (HSH-9 and HSH-16 only)", entry, basis);
-  if (int st = check_coef_layout(entry, layout)) return st;
-  return check_coef_stride(entry, coef_view(static_cast<const float*>(nullptr), layout, basis_terms(basis), P, stride),
-                           P, 3);
-}
-
-// pixel-major rows as 16-byte pieces: every wave's run of every channel starts on a 16-byte boundary
-inline int maps_vec(const float* coef, int layout, int64_t cs) {
-  return layout == RTI_COEF_PIXEL_MAJOR && aligned_to(coef, 16) && cs % 4 == 0 ? 1 : 0;
+  return check_rgb_maps(entry, basis_terms(basis), layout, stride, P);
 }
 
 }  // namespace
@@ -336,14 +206,19 @@ extern "C" int rti_hsh_qparams(const float* coef, int basis, int coef_layout, in
   const int64_t cs = coef_channel_stride ? coef_channel_stride : P * k;
   const int blocks = (int)qparams_blocks(P, CHUNK);
   float* partial = static_cast<float*>(workspace);
-  const HshArgs a{coef, coef_layout, cs, P, maps_vec(coef, coef_layout, cs), (hipStream_t)stream};
+  const int vin = maps_staged(coef, coef_layout, 3, cs);
+  const hipStream_t s = (hipStream_t)stream;
   note_launches(2);
-  with_k_layout(k, coef_layout, Extremes{a, blocks, partial});
+  with_hsh_terms(k, [&](auto kt) {
+    with_layout(coef_layout, [&](auto l) {
+      hipLaunchKernelGGL((hsh_extremes_k<decltype(kt)::value, decltype(l)::value>), dim3(blocks), dim3(256), 0, s, coef,
+                         cs, P, vin, partial);
+    });
+  });
   if (int st = check_launch(E)) return st;
-  if (k == 9)
-    hipLaunchKernelGGL(hsh_qparams_k<9>, dim3(1), dim3(256), 0, a.s, partial, blocks, qparams);
-  else
-    hipLaunchKernelGGL(hsh_qparams_k<16>, dim3(1), dim3(256), 0, a.s, partial, blocks, qparams);
+  with_hsh_terms(k, [&](auto kt) {
+    hipLaunchKernelGGL(hsh_qparams_k<decltype(kt)::value>, dim3(1), dim3(256), 0, s, partial, blocks, qparams);
+  });
   return check_launch(E);
 }
 
@@ -355,9 +230,14 @@ extern "C" int rti_hsh_quantise(const float* coef, int basis, int coef_layout, i
   if (!aligned_to(qparams, 4)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 4-byte aligned", E);
   const int k = basis_terms(basis);
   const int64_t cs = coef_channel_stride ? coef_channel_stride : P * k;
-  const HshArgs a{coef, coef_layout, cs, P, maps_vec(coef, coef_layout, cs), (hipStream_t)stream};
+  const int vin = maps_staged(coef, coef_layout, 3, cs), vout = aligned_to(coef8, 16) ? 1 : 0;
   note_launches(1);
-  with_k_layout(k, coef_layout, Quantise{a, aligned_to(coef8, 16) ? 1 : 0, qparams, coef8});
+  with_hsh_terms(k, [&](auto kt) {
+    with_layout(coef_layout, [&](auto l) {
+      hipLaunchKernelGGL((hsh_quantise_k<decltype(kt)::value, decltype(l)::value>), dim3(grid_1d(P, CHUNK)), dim3(256), 0,
+                         (hipStream_t)stream, coef, cs, P, vin, vout, qparams, coef8);
+    });
+  });
   return check_launch(E);
 }
 
@@ -367,16 +247,17 @@ extern "C" int rti_relight_hsh8(const uint8_t* coef8, int basis, int64_t P, cons
   if (int st = check_pointers(E, {coef8, qparams, luv, out})) return st;
   if (P < 1 || E_ < 1) return fail(RTI_ERR_BAD_ARG, "%s: P and E must be positive", E);
   if (!hsh_basis(basis)) return fail(RTI_ERR_UNSUPPORTED, "%s: basis %d (HSH-9 and HSH-16 only)", E, basis);
-  if (out_dtype != RTI_F32 && out_dtype != RTI_I32 && out_dtype != RTI_U8)
-    return fail(RTI_ERR_UNSUPPORTED, "%s: out dtype %d", E, out_dtype);
+  if (int st = check_out_dtype(E, out_dtype)) return st;
   if (!aligned_to(qparams, 4)) return fail(RTI_ERR_BAD_ARG, "%s: qparams must be 4-byte aligned", E);
   const int vin = aligned_to(coef8, 16) ? 1 : 0;
-  // a wave's 192 output elements as dwords: direction e's rows start 3·P·e elements into out
-  const int vout = aligned_to(out, 4) && (out_dtype != RTI_U8 || P % 4 == 0) ? 1 : 0;
+  const int vout = hsh_render::rows_as_dwords(out, out_dtype, P);
   note_launches(1);
-  if (basis == RTI_BASIS_HSH9)
-    launch_relight8_out<9>(out_dtype, coef8, P, vin, vout, qparams, luv, E_, out, (hipStream_t)stream);
-  else
-    launch_relight8_out<16>(out_dtype, coef8, P, vin, vout, qparams, luv, E_, out, (hipStream_t)stream);
+  with_hsh_terms(basis_terms(basis), [&](auto kt) {
+    with_out(out_dtype, [&](auto t) {
+      using TO = decltype(t);
+      hipLaunchKernelGGL((relight_hsh8_k<decltype(kt)::value, TO>), dim3(grid_1d(P, CHUNK)), dim3(256), 0,
+                         (hipStream_t)stream, coef8, P, vin, vout, qparams, luv, E_, static_cast<TO*>(out));
+    });
+  });
   return check_launch(E);
 }

@@ -33,6 +33,7 @@
 #include <cstdint>
 
 #include "rti_basis.h"
+#include "rti_dispatch.h"
 #include "rti_hsh_px.h"
 #include "rti_stack.h"
 
@@ -254,6 +255,8 @@ hsh_normals_k(Source src, int64_t P, int G, int E, const u32x4* __restrict__ tab
 
   // every lane stays to the end: the workgroup fills the table together
   const int64_t wave_px = (int64_t)blockIdx.x * CHUNK + wave * (64 * NPX);
+  // the two sources are rti_hsh_px.h's load_px8 and load_px written out: as calls they move the occupancy of 11 of the
+  // 20 instantiations of this kernel, the one that arithmetic bounds
   float l[NPX][K];
 #pragma unroll
   for (int s = 0; s < NPX; ++s) {
@@ -354,31 +357,15 @@ struct Launch {
   hipStream_t s;
 };
 
-template <int K, int C, int CL, int NL>
-void launch_t(const Launch& a) {
+// C = 0: the 8-bit map
+template <int K, int C, int CL>
+void launch(const Launch& a, int nl) {
   constexpr int IN_SLAB = C == 0 ? slab_v4(run_v4<3 * K>(), 0) : CL == RTI_COEF_PIXEL_MAJOR ? slab_v4(run_v4<4 * K>(), 0) : 0;
   const size_t lds_bytes = (size_t)lds_v4(K, a.E, IN_SLAB) * 16;  // at most 51008 + 3072 bytes: under the 64 KiB default
-  hipLaunchKernelGGL((hsh_normals_k<K, C, CL, NL>), dim3(grid_1d(a.P, CHUNK)), dim3(256), lds_bytes, a.s, a.src, a.P,
-                     a.G, a.E, static_cast<const u32x4*>(a.table), a.dst);
-}
-
-template <int K, int C, int CL>
-void launch_nl(const Launch& a, int nl) {
-  if (nl == RTI_NORMAL_PLANAR) launch_t<K, C, CL, RTI_NORMAL_PLANAR>(a);
-  else launch_t<K, C, CL, RTI_NORMAL_PIXEL_MAJOR>(a);
-}
-
-template <int K, int C>
-void launch_cl(const Launch& a, int cl, int nl) {
-  if (cl == RTI_COEF_PLANAR) launch_nl<K, C, RTI_COEF_PLANAR>(a, nl);
-  else launch_nl<K, C, RTI_COEF_PIXEL_MAJOR>(a, nl);
-}
-
-template <int K>
-void launch_c(const Launch& a, int C, int cl, int nl) {
-  if (C == 0) launch_nl<K, 0, RTI_COEF_PIXEL_MAJOR>(a, nl);
-  else if (C == 1) launch_cl<K, 1>(a, cl, nl);
-  else launch_cl<K, 3>(a, cl, nl);
+  with_normal_layout(nl, [&](auto n) {
+    hipLaunchKernelGGL((hsh_normals_k<K, C, CL, decltype(n)::value>), dim3(grid_1d(a.P, CHUNK)), dim3(256), lds_bytes, a.s,
+                       a.src, a.P, a.G, a.E, static_cast<const u32x4*>(a.table), a.dst);
+  });
 }
 
 // ---- checks -------------------------------------------------------------------------------------------------------
@@ -393,8 +380,7 @@ int check_basis_grid(const char* entry, int basis, int grid) {
 // what the two map entries share after their own map checks; fills the weights
 int check_search(const char* entry, int basis, int normal_layout, int grid, const float* w, const void* table,
                  float (&weights)[3]) {
-  if (normal_layout != RTI_NORMAL_PIXEL_MAJOR && normal_layout != RTI_NORMAL_PLANAR)
-    return fail(RTI_ERR_BAD_ARG, "%s: normal layout %d", entry, normal_layout);
+  if (int st = check_normal_layout(entry, normal_layout)) return st;
   if (int st = check_basis_grid(entry, basis, grid)) return st;
   weights[0] = w ? w[0] : 0.299f;
   weights[1] = w ? w[1] : 0.587f;
@@ -445,13 +431,17 @@ extern "C" int rti_hsh_normals(const float* coef, int basis, int coef_layout, in
   const int k = basis_terms(basis);
   if (int st = check_coef_stride(E, coef_view(coef, coef_layout, k, P, coef_channel_stride), P, C)) return st;
   const int64_t cs = coef_channel_stride ? coef_channel_stride : P * k;
-  // pixel-major rows as 16-byte pieces: every run of every channel read starts on a 16-byte boundary
-  const int vin = coef_layout == RTI_COEF_PIXEL_MAJOR && aligned_to(coef, 16) && (C == 1 || cs % 4 == 0) ? 1 : 0;
+  const int vin = maps_staged(coef, coef_layout, C, cs);
   const Launch a{Source{coef, nullptr, nullptr, cs, vin, {weights[0], weights[1], weights[2]}}, P, grid,
                  grid_points(grid), table, Sink{normals, kind, peak}, (hipStream_t)stream};
   note_launches(1);
-  if (k == 9) launch_c<9>(a, C, coef_layout, normal_layout);
-  else launch_c<16>(a, C, coef_layout, normal_layout);
+  with_hsh_terms(k, [&](auto kt) {
+    with_channels(C, [&](auto ct) {
+      with_layout(coef_layout, [&](auto l) {
+        launch<decltype(kt)::value, decltype(ct)::value, decltype(l)::value>(a, normal_layout);
+      });
+    });
+  });
   return check_launch(E);
 }
 
@@ -467,7 +457,7 @@ extern "C" int rti_hsh8_normals(const uint8_t* coef8, int basis, int64_t P, cons
   const Launch a{Source{nullptr, coef8, qparams, 0, aligned_to(coef8, 16) ? 1 : 0, {weights[0], weights[1], weights[2]}},
                  P, grid, grid_points(grid), table, Sink{normals, kind, peak}, (hipStream_t)stream};
   note_launches(1);
-  if (basis == RTI_BASIS_HSH9) launch_c<9>(a, 0, RTI_COEF_PIXEL_MAJOR, normal_layout);
-  else launch_c<16>(a, 0, RTI_COEF_PIXEL_MAJOR, normal_layout);
+  with_hsh_terms(basis_terms(basis),
+                 [&](auto kt) { launch<decltype(kt)::value, 0, RTI_COEF_PIXEL_MAJOR>(a, normal_layout); });
   return check_launch(E);
 }

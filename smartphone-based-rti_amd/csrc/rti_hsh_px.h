@@ -1,7 +1,7 @@
-// rti_hsh_px.h -- what the HSH translation units share (rti_hsh8.hip, rti_hsh_normals.hip): rti_relight's fp32
-// chain, a wave's run of 64 rows through its LDS slab, and the dequantisation of an 8-bit pixel.
-// Everything is __forceinline__ device code with one pixel per lane and 64 consecutive pixels per wave; moving it
-// here changed no instruction of rti_hsh8.hip's kernels.
+// rti_hsh_px.h -- what the kernels with one HSH pixel per lane share (rti_hsh8.hip, rti_hsh_normals.hip, and through
+// rti_hsh_render_px.h rti_hsh_specular.hip and rti_hsh_gain.hip): rti_relight's fp32 chain, a wave's run of 64 rows
+// through its LDS slab, and the two sources of a lane's pixel, the 8-bit payload and the fp32 maps (DESIGN.md §4.9,
+// §4.18).  The device code is __forceinline__, with 64 consecutive pixels per wave.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -134,6 +134,58 @@ __device__ __forceinline__ void dequantise_px(const uint32_t (&w)[(3 * K + 3) / 
       c[ch][j] = t + bias;
     }
   }
+}
+
+// ---- the two sources of a lane's pixel --------------------------------------------------------------------------
+// Pixel run_px + lane of a run of 64.  staged is wave-uniform: a full run whose rows may move as 16-byte pieces (the
+// entry's alignment checks).  Otherwise a live lane loads its own values.
+
+// c[ch][j] of the 8-bit payload [p][ch][j]; qs: load_steps'.  A lane past the image dequantises zero bytes.
+template <int K>
+__device__ __forceinline__ void load_px8(const uint8_t* __restrict__ coef8, int64_t run_px, int lane, bool live,
+                                         bool staged, u32x4* __restrict__ slab, const float* __restrict__ qs,
+                                         float (&c)[3][K]) {
+  constexpr int NB = 3 * K, NW = (NB + 3) / 4;
+  uint32_t w[NW];
+#pragma unroll
+  for (int i = 0; i < NW; ++i) w[i] = 0;
+  if (staged) {
+    run_in<NB>(coef8 + run_px * NB, lane, slab);
+    lane_words<NB>(slab, lane, w);
+  } else if (live) {
+    const int64_t p = run_px + lane;
+#pragma unroll
+    for (int i = 0; i < NB; ++i) w[i >> 2] |= (uint32_t)coef8[p * NB + i] << (8 * (i & 3));
+  }
+  dequantise_px<K>(w, qs, c);
+}
+
+// c[ch][j] of C fp32 maps cs elements apart in layout CL: a pixel-major channel's 64 rows are one run when staged,
+// planar maps are coalesced as they are.  A lane past the image gets `dead`.
+template <int K, int C, int CL>
+__device__ __forceinline__ void load_px(const float* coef, int64_t cs, int64_t P, int64_t run_px, int lane, bool live,
+                                        bool staged, float dead, u32x4* slab, float (&c)[C][K]) {
+  const int64_t p = run_px + lane;
+#pragma unroll
+  for (int ch = 0; ch < C; ++ch) {
+    const float* map = coef + ch * cs;
+    if (CL == RTI_COEF_PIXEL_MAJOR && staged) {
+      run_in<4 * K>(map + run_px * K, lane, slab);
+      uint32_t w[K];
+      lane_words<4 * K>(slab, lane, w);
+#pragma unroll
+      for (int j = 0; j < K; ++j) c[ch][j] = __uint_as_float(w[j]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < K; ++j)
+        c[ch][j] = !live ? dead : CL == RTI_COEF_PLANAR ? map[(int64_t)j * P + p] : map[p * K + j];
+    }
+  }
+}
+
+// host: staged may hold for fp32 maps, every run of every channel read starts on a 16-byte boundary
+inline int maps_staged(const float* coef, int coef_layout, int C, int64_t cs) {
+  return coef_layout == RTI_COEF_PIXEL_MAJOR && aligned_to(coef, 16) && (C == 1 || cs % 4 == 0) ? 1 : 0;
 }
 
 }  // namespace hsh_px
