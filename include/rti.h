@@ -26,6 +26,7 @@
 #ifndef RTI_H
 #define RTI_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -1114,6 +1115,61 @@ int rti_relight_hsh_gain(const float* coef, int basis, int coef_layout, int C, i
 int rti_relight_hsh8_gain(const uint8_t* coef8, int basis, int64_t P, const float* qparams,
                           const float* normals, int normal_layout, double gain,
                           const double* luv /* HOST [E][2] */, int E, void* out, int out_dtype, rti_stream_t stream);
+
+/* ---- device: surface height from a normal map, masked Poisson integration (rti_height.hip) -----------------------
+ * The reference has no integrator; the semantics are build-defined.
+ * Input: normals, fp32, dense, H x W, [y][x][3] (RTI_NORMAL_PIXEL_MAJOR) or [3][y][x] (RTI_NORMAL_PLANAR).  x is the
+ *   column index and y the row index.  The height z satisfies dz/dx = -n_x/n_z and dz/dy = -n_y/n_z; flip_y != 0
+ *   negates the y-gradient, for maps whose y component points up the image.
+ * Validity: a pixel is valid when its three components are finite and n_z >= nz_min, nz_min in (0, 1]; the kind-4 NaN
+ *   pixels and the kind-1 edge normals with n_z = 0 of the normal entries fall out this way.  A valid pixel with no
+ *   valid 4-neighbour carries no height information and is invalid too.
+ * Gradients, per valid pixel, in fp64 from the fp32 components, each quotient rounded once:
+ *     p = -((double)n_x/(double)n_z),   q = -((double)n_y/(double)n_z), or +(...) under flip_y
+ * The problem: the least-squares surface over the graph of valid pixels with an edge between valid 4-neighbours,
+ *     minimise  sum over edges (z_j - z_i - g_ij)^2
+ *   with g_ij = (p_i + p_j)/2 for a horizontal edge (i left of j) and (q_i + q_j)/2 for a vertical one (i above j):
+ *   the midpoint functional, exact for quadratic surfaces.  No boundary condition: holes and irregular outlines are
+ *   natural boundaries.  Normal equations A z = b: A the graph Laplacian, b_i = sum over the neighbours j of -g_ij with
+ *   the edge oriented from i, summed in the order left, right, up, down in fp64 with no contraction.
+ * Gauge: the null space is one constant per connected component.  The entry subtracts the mean of z over ALL valid
+ *   pixels (one fixed-order fp64 reduction at the end); separate components float independently of each other.
+ * Output: height fp32 [H][W], NaN at invalid pixels; valid (NULL ok) uint8 [H][W], 1 / 0.
+ * Solver: preconditioned conjugate gradients in fp64 on the device from z = 0, or from z0 (NULL ok; fp32 [H][W], read
+ *   only at valid pixels, where it must be finite; it may be the height array itself).  It stops when
+ *   |r|_2 <= rtol*|b|_2 or after max_iters iterations (0 returns the start with its residual); |b|_2 = 0 returns z = 0
+ *   with 0 iterations and no division.  Not converging is not an error: RTI_OK and stats[1] = -1.
+ *   precond = RTI_HEIGHT_JACOBI: the diagonal (the valid degree).  RTI_HEIGHT_MULTIGRID: one symmetric V-cycle of
+ *   unsmoothed 2x2 aggregation multigrid in fp64: level l+1 is ceil(H_l/2) x ceil(W_l/2), a coarse cell exists when
+ *   any child does, its edges carry the summed fine weights crossing between the two cells (the Galerkin operator),
+ *   restriction sums the children's residuals, prolongation copies the coarse correction times 2 (over-correction),
+ *   2 + 2 sweeps of weighted Jacobi (0.8) from a zero guess, levels stop at max(H_l, W_l) <= 4 where 8 sweeps run and
+ *   no exact solve (the operator is singular); cells of degree 0 on any level keep a zero correction.  The
+ *   preconditioner is one fixed, symmetric, linear operator throughout a solve.
+ *   Dot products are two-stage fixed-order reductions (no atomics), so one call gives the same bits run to run; the
+ *   PCG scalars stay in device memory.  No kernel waits on another workgroup.
+ * Synchronisation: the host reads |r|^2 back through the workspace every check_every iterations, in [1, 1024], and
+ *   once after set-up and once at the end, and SYNCHRONISES stream each time: the entry is not capturable in a
+ *   hipGraph.  The host overshoots by at most check_every - 1 iterations.  No allocation.
+ * workspace: device, 256-byte aligned, the bytes the size query returns (0 on bad arguments; a function of H*W and
+ *   precond alone, monotone in H*W); it need not be initialised.  The level count query answers -1 on bad sizes.
+ * stats (HOST [6], NULL ok): iterations run; the iteration at which the criterion was first met on the device (0 = the
+ *   start met it), or -1; the final recursive |r|/|b|; the true |b - A z|/|b| recomputed once at the end; the count
+ *   of valid pixels; |b|_2.  With |b|_2 = 0: 0, 0, 0, 0, the count, 0.
+ * Every argument check answers before any HIP call.  RTI_ERR_BAD_ARG: null normals, workspace or height; H or W < 1;
+ *   H*W >= 2^31; a bad layout or precond; nz_min outside (0, 1]; rtol not finite or < 0; max_iters outside
+ *   [0, 100000]; check_every outside [1, 1024]; workspace off 256 bytes; height overlapping normals.
+ * Not built: per-edge confidence weights, robust (L1 / total-variation) integration for depth discontinuities,
+ *   perspective cameras, a per-component gauge, a multi-GPU wrapper, an entry that takes gradients, mesh export. */
+#define RTI_HEIGHT_MULTIGRID 0
+#define RTI_HEIGHT_JACOBI    1
+int    rti_height_levels(int H, int W);
+size_t rti_height_workspace_bytes(int H, int W, int precond);
+int    rti_height_from_normals(const float* normals, int normal_layout, int H, int W,
+                               double nz_min, int flip_y, const float* z0 /* NULL ok */,
+                               double rtol, int max_iters, int check_every, int precond,
+                               void* workspace, float* height, uint8_t* valid /* NULL ok */,
+                               double* stats /* HOST [6], NULL ok */, rti_stream_t stream);
 
 #ifdef __cplusplus
 }

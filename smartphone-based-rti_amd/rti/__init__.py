@@ -50,6 +50,9 @@ bara96/Smartphone-based-RTI: analysis.py:196-411, interactive_relighting.py:11-3
     rgb = rti.relight_hsh8_specular(h, n, 0.3, -0.2, kd=0.4, ks=150, exp=75, out_dtype=torch.uint8)  # one launch a frame
     rgb = rti.relight_hsh8_gain(h, n, 0.3, -0.2, gain=3.5, out_dtype=torch.uint8)  # diffuse gain about the same normals
 
+    n, albedo = rti.photometric_stereo(I, lu, lv)    # normals to geometry: the least-squares height map, on the GPU
+    z = rti.height_from_normals(n)                   # [H, W] in pixel units, zero mean, NaN where the normal is unusable
+
 Compute runs in HIP kernels of librti.so (include/rti.h); importing this
 package does not touch the GPU.
 """
@@ -74,7 +77,8 @@ from .api import (BASES, FitAccumulator, apply_operator, basis_eval, basis_id, b
                   relight_rgb, relight_rgb_into, relight_rgb_enhanced, relight_rgb_enhanced_into, rgb_normals,
                   rgb_normals_into,
                   relight_hsh_specular, relight_hsh_specular_into, relight_hsh8_specular, relight_hsh8_specular_into,
-                  relight_hsh_gain, relight_hsh_gain_into, relight_hsh8_gain, relight_hsh8_gain_into)
+                  relight_hsh_gain, relight_hsh_gain_into, relight_hsh8_gain, relight_hsh8_gain_into,
+                  height_from_normals, height_from_normals_into, height_levels, height_workspace)
 from .io import read_ptm, read_ptm8, read_rti, write_ptm, write_rti
 
 __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_into", "fit_chunked",
@@ -99,7 +103,8 @@ __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_in
            "relight_rgb_enhanced", "relight_rgb_enhanced_into", "rgb_normals", "rgb_normals_into",
            "relight_hsh_specular", "relight_hsh_specular_into", "relight_hsh8_specular",
            "relight_hsh8_specular_into", "relight_hsh_gain", "relight_hsh_gain_into", "relight_hsh8_gain",
-           "relight_hsh8_gain_into", "read_ptm", "read_ptm8", "write_ptm",
+           "relight_hsh8_gain_into", "height_from_normals", "height_from_normals_into", "height_levels",
+           "height_workspace", "read_ptm", "read_ptm8", "write_ptm",
            "read_rti", "write_rti", "library_path", "load"]
 
 __version__ = "0.1.0"

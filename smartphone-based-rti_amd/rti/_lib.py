@@ -41,6 +41,8 @@ RTI_ENHANCE_DIFFUSE_GAIN = 1  # rti_relight_enhanced modes
 RTI_ENHANCE_SPECULAR = 2
 RTI_UNSHARP_MAX_RADIUS = 32  # rti_map_unsharp: the largest Gaussian radius
 RTI_SPECULAR_MAX_DIRS = 16  # rti_relight_hsh_specular, rti_relight_hsh_gain: the most directions of a launch
+RTI_HEIGHT_MULTIGRID = 0  # rti_height_from_normals preconditioners
+RTI_HEIGHT_JACOBI = 1
 
 RTI_KERNEL_AUTO = 0
 RTI_KERNEL_VALU = 1
@@ -214,6 +216,11 @@ SIGNATURES = {
                                       _c_double_p, _c_int, _c_void_p, _c_int, _c_void_p]),
     "rti_relight_hsh8_gain": (_c_int, [_c_void_p, _c_int, _c_i64, _c_void_p, _c_void_p, _c_int, _c_double,
                                        _c_double_p, _c_int, _c_void_p, _c_int, _c_void_p]),
+    "rti_height_levels": (_c_int, [_c_int, _c_int]),
+    "rti_height_workspace_bytes": (ctypes.c_size_t, [_c_int, _c_int, _c_int]),
+    "rti_height_from_normals": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_double, _c_int, _c_void_p, _c_double,
+                                         _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_double_p,
+                                         _c_void_p]),
 }
 
 _lock = threading.Lock()

@@ -2655,6 +2655,106 @@ def relight_hsh8_gain(q, n, lu, lv, *, gain=1.0, normal_layout="pixel", out_dtyp
     return out[0] if scalar else out
 
 
+# ---- surface height from a normal map: masked Poisson integration (rti_height.hip) ------------
+
+HEIGHT_PRECONDS = {"multigrid": L.RTI_HEIGHT_MULTIGRID, "jacobi": L.RTI_HEIGHT_JACOBI}
+
+
+def _height_precond_id(precond):
+    if isinstance(precond, int) and not isinstance(precond, bool):
+        return precond
+    try:
+        return HEIGHT_PRECONDS[precond]
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown preconditioner {precond!r} (expected one of {sorted(HEIGHT_PRECONDS)})") from None
+
+
+def _height_dims(n, nl):
+    """A dense fp32 normal map [H, W, 3] (pixel-major) or [3, H, W] (planar) on the GPU -> (H, W)."""
+    if torch.is_tensor(n) and n.dtype == torch.float32 and (n.dim() != 3 or n.shape[2 if nl == 0 else 0] != 3):
+        raise ValueError(f"n must be a normal map [H, W, 3] (pixel) or [3, H, W] (planar); got {tuple(n.shape)}")
+    _, H, W = _map_dims(n, nl)  # the dtype and the shape are judged before the device
+    return H, W
+
+
+def height_levels(H, W):
+    """Grids of the aggregation hierarchy of an H×W map (``rti_height_levels``, host)."""
+    n = L.lib().rti_height_levels(int(H), int(W))
+    if n < 1:
+        raise ValueError(f"H and W must be positive with H·W below 2^31; got {H}×{W}")
+    return n
+
+
+def height_workspace(H, W, precond="multigrid", device="cuda"):
+    """The device scratch of ``height_from_normals_into`` for an H×W map: an uninitialised uint8 tensor of
+    ``rti_height_workspace_bytes`` bytes on ``device`` (the one allocation of a solve; reusable across solves)."""
+    nbytes = L.lib().rti_height_workspace_bytes(int(H), int(W), _height_precond_id(precond))
+    if nbytes <= 0:
+        raise ValueError(f"H and W must be positive with H·W below 2^31 and precond known; got {H}×{W}, {precond!r}")
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+
+
+def height_from_normals_into(n, workspace, height, *, valid=None, z0=None, nz_min=0.1, flip_y=False, rtol=1e-6,
+                             max_iters=2000, check_every=8, precond="multigrid", layout="pixel", stats=None):
+    """Launch ``rti_height_from_normals`` on preallocated tensors (no allocation; it synchronises the stream every
+    ``check_every`` iterations, so it is not graph-capturable).
+
+    n: contiguous CUDA fp32 [H, W, 3] (layout="pixel") or [3, H, W] ("planar"); workspace: ``height_workspace``;
+    height: fp32 [H, W]; valid: uint8 [H, W] or None; z0: fp32 [H, W] or None (it may be ``height``); stats: a
+    float64 NumPy array of 6 or None.  Returns height."""
+    nl = _normal_layout_id(layout)
+    H, W = _height_dims(n, nl)
+    pc = _height_precond_id(precond)
+    need = L.lib().rti_height_workspace_bytes(H, W, pc)
+    if need <= 0:
+        raise ValueError(f"H·W must be below 2^31 and precond known; got {H}×{W}, {precond!r}")
+    ws = _workspace_arg(workspace, need, n)
+    if stats is not None and (not isinstance(stats, np.ndarray) or stats.dtype != np.float64 or stats.size != 6
+                              or not stats.flags.c_contiguous):
+        raise ValueError("stats must be a contiguous float64 NumPy array of 6 values")
+    st = L.lib().rti_height_from_normals(
+        _vp(n), nl, H, W, float(nz_min), int(bool(flip_y)),
+        None if z0 is None else _map_out(z0, "z0", torch.float32, H * W, n), float(rtol), int(max_iters),
+        int(check_every), pc, ws, _map_out(height, "height", torch.float32, H * W, n),
+        None if valid is None else _map_out(valid, "valid", torch.uint8, H * W, n),
+        None if stats is None else _dptr(stats), _stream_of(n))
+    L.check(st, "rti_height_from_normals")
+    return height
+
+
+def height_from_normals(n, nz_min=0.1, flip_y=False, rtol=1e-6, max_iters=2000, precond="multigrid", z0=None,
+                        layout="pixel", return_valid=False, stats=None, check_every=8):
+    """The height (depth) map of a normal map on the GPU (``rti_height_from_normals``): the least-squares surface
+    with ∂z/∂x = −n_x/n_z, ∂z/∂y = −n_y/n_z (x the column, y the row; ``flip_y`` negates the y-gradient) over the
+    valid pixels -- finite normals with n_z >= nz_min and a valid 4-neighbour -- in pixel units, zero mean over
+    the valid pixels, NaN elsewhere.  Holes and irregular outlines are natural boundaries; separate components
+    float independently.  Preconditioned conjugate gradients in fp64 until ‖r‖ <= rtol·‖b‖ or max_iters;
+    precond "multigrid" (aggregation V-cycle) or "jacobi".  Not converging is not an error: see stats.
+
+    n: CUDA fp32 [H, W, 3] (layout="pixel") or [3, H, W] ("planar"), e.g. of ``photometric_stereo``, ``normals``,
+    ``hsh_normals``; z0: None or a start [H, W] fp32; stats: None or a float64 NumPy array of 6 that receives
+    iterations run, the iteration the criterion was met (−1: not), the final recursive and the true relative
+    residual, the count of valid pixels and ‖b‖.  Returns [H, W] fp32, with return_valid (height, valid uint8
+    [H, W]).  Allocates the workspace (``height_workspace``).  Not built: confidence weights, robust (L1)
+    integration, perspective cameras, a per-component gauge, ``rti.parallel``."""
+    nl = _normal_layout_id(layout)
+    if not torch.is_tensor(n):
+        raise ValueError("n must be a CUDA (HIP) tensor")
+    src = n.contiguous()
+    H, W = _height_dims(src, nl)
+    if z0 is not None:
+        _require_cuda(z0, "z0")
+        if tuple(z0.shape) != (H, W) or z0.dtype != torch.float32:
+            raise ValueError(f"z0 must be a float32 [{H}, {W}] tensor; got {z0.dtype} {tuple(z0.shape)}")
+        z0 = z0.contiguous()
+    ws = height_workspace(H, W, precond, src.device)
+    height = torch.empty((H, W), dtype=torch.float32, device=src.device)
+    valid = torch.empty((H, W), dtype=torch.uint8, device=src.device) if return_valid else None
+    height_from_normals_into(src, ws, height, valid=valid, z0=z0, nz_min=nz_min, flip_y=flip_y, rtol=rtol,
+                             max_iters=max_iters, check_every=check_every, precond=precond, layout=nl, stats=stats)
+    return (height, valid) if return_valid else height
+
+
 # ---- light operators (RBF, fused PTM/HSH fit + evaluation) ----------------------------------
 
 def _query(qu, qv):

@@ -4,7 +4,7 @@
 ``lrgb_quantise`` / ``relight_lrgb8`` / ``hsh_quantise`` / ``relight_hsh8`` / ``hsh_normals`` / ``hsh8_normals`` /
 ``rgb8_quantise`` / ``relight_rgb8`` / ``rgb8_normals`` / ``relight_lrgb_enhanced`` / ``relight_lrgb8_enhanced`` /
 ``relight_rgb8_enhanced`` / ``relight_rgb`` / ``relight_rgb_enhanced`` / ``rgb_normals`` / ``relight_hsh_specular`` /
-``relight_hsh8_specular`` / ``relight_hsh_gain`` / ``relight_hsh8_gain``.
+``relight_hsh8_specular`` / ``relight_hsh_gain`` / ``relight_hsh8_gain`` / ``height_from_normals``.
 
 They let the fit and relight kernels sit inside torch programs (and
 ``torch.library`` fake-tensor tracing) while the compute stays in librti's
@@ -883,3 +883,23 @@ def relight_hsh8_gain(coef8: torch.Tensor, qparams: torch.Tensor, n: torch.Tenso
 @relight_hsh8_gain.register_fake
 def _(coef8, qparams, n, luv, gain=1.0, normals_planar=False, out_dtype=torch.float32):
     return coef8.new_empty((luv.shape[0], coef8.shape[0], 3), dtype=out_dtype)
+
+
+@torch.library.custom_op("rti::height_from_normals", mutates_args=())
+def height_from_normals(n: torch.Tensor, nz_min: float = 0.1, flip_y: bool = False, rtol: float = 1e-6,
+                        max_iters: int = 2000, jacobi: bool = False, z0: torch.Tensor | None = None,
+                        planar: bool = False, check_every: int = 8) -> torch.Tensor:
+    """The height map of a normal map (``rti_height_from_normals``).  n CUDA fp32 [H, W, 3] (or [3, H, W] if
+    planar), z0 None or a start fp32 [H, W] -> fp32 [H, W], zero mean over the valid pixels, NaN elsewhere;
+    jacobi selects the diagonal preconditioner instead of the multigrid V-cycle."""
+    api._require_cuda(n, "n")
+    if z0 is not None:
+        api._require_cuda(z0, "z0")
+        _same_device(n=n, z0=z0)
+    return api.height_from_normals(n, nz_min, flip_y, rtol, max_iters, "jacobi" if jacobi else "multigrid", z0,
+                                   "planar" if planar else "pixel", check_every=check_every)
+
+
+@height_from_normals.register_fake
+def _(n, nz_min=0.1, flip_y=False, rtol=1e-6, max_iters=2000, jacobi=False, z0=None, planar=False, check_every=8):
+    return n.new_empty(tuple(n.shape[1:]) if planar else tuple(n.shape[:2]))
