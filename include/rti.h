@@ -1171,6 +1171,93 @@ int    rti_height_from_normals(const float* normals, int normal_layout, int H, i
                                void* workspace, float* height, uint8_t* valid /* NULL ok */,
                                double* stats /* HOST [6], NULL ok */, rti_stream_t stream);
 
+/* ---- device: multi-light detail enhancement (rti_multilight.hip) ----------------------------------
+ * RTIViewer's static / dynamic multi-light mode (Palma, Corsini, Cignoni, Scopigno, Mudge 2010): for every small tile
+ * of the image the light, out of E candidates near the user's light, that shows the tile's relief best (local
+ * sharpness plus brightness); the per-tile choice smoothed into a light field; the image relit with a light direction
+ * per pixel.  The reference has none of it; the semantics are build-defined.  Every expression below is evaluated left
+ * to right as written, every operation rounded, nothing contracted except the fused multiply-adds named.
+ * Common to the three entries: the image is H x W with pixel p = y·W + x and H·W < 2^31.  Maps: device fp32, C = 1 or 3
+ * maps as rti_fit_shared writes them, [c][p][k] (RTI_COEF_PIXEL_MAJOR) or [c][k][p] (RTI_COEF_PLANAR),
+ * coef_channel_stride in elements, 0 = dense = k·P (one map never uses it); basis PTM-6, HSH-9 or HSH-16.  The tile
+ * edge T is 8, 16 or 32; tile (ty, tx) covers the rows [ty·T, min((ty+1)·T, H)) and the columns likewise;
+ * Ty = ceil(H/T), Tx = ceil(W/T); tile arrays are [Ty][Tx] row-major.
+ * rti_light_scores (the search; one launch, one workgroup per tile, the maps read once, 16·E bytes out per tile):
+ *   luminance map   C = 1: l_j = c_j.  C = 3: l_j = (wR·r_j + wG·g_j) + wB·b_j in fp32 as rti_hsh_normals forms it; w:
+ *                   three fp32 weights on the HOST, NULL = (0.299f, 0.587f, 0.114f).
+ *   candidates      luv: fp64 [E][2] on the HOST, 1 <= E <= RTI_LIGHT_MAX_CANDIDATES, every value finite (they travel
+ *                   as one kernel argument, 64 × 16 bytes).
+ *   usable          a pixel all k of whose l_j are finite; this does not depend on the candidate.
+ *   value           V_e(x, y) = rti_relight's F32 value of the luminance map at candidate e, bit for bit: the same
+ *                   basis_eval<float> of ((float)lu_e, (float)lv_e) and the same chain acc = l_0·b_0,
+ *                   acc = fmaf(l_j, b_j, acc) for j = 1..k−1.
+ *   S_e             the fp64 sum of d·d over every pair of usable pixels inside the tile that are horizontal or vertical
+ *                   neighbours, d = (double)V_e(second) − (double)V_e(first) (exact); n_S = the number of pairs.  No
+ *                   pixel outside the tile is read: pairs across a tile edge do not count.
+ *   B_e             the fp64 sum of (double)V_e over the tile's n_P usable pixels.
+ *   scores          device fp64 [Ty][Tx][E][2], 8-byte aligned: sharp_e = S_e/(double)n_S, or 0 if n_S = 0;
+ *                   bright_e = B_e/(double)n_P, or 0 if n_P = 0.
+ *   count           NULL or device int32 [Ty][Tx]: n_P.
+ *   The order of the two sums is the kernel's own (per lane, then over the wave, then over the waves, each fixed): a
+ *   call gives the same bits run to run, and sharp_e lies within (n_S + 2)·2^-53 (relative) of the exact quotient,
+ *   bright_e within (n_P + 1)·2^-53·mean|V_e|.  No floating-point atomics.
+ * rti_light_field (the choice and its smoothing; 1 + smooth launches of a thread per tile):
+ *   scores, count   as rti_light_scores wrote them (count is required); luv, E: the same candidates.
+ *   per tile, fp64  Smax = the largest sharp_e and Bmax the largest bright_e over e, each raised from 0 with `>` (a NaN
+ *                   never raises it).  s_e = sharp_e/Smax if Smax > 0, else 0; b_e = bright_e/Bmax if Bmax > 0, else 0;
+ *                   score_e = ws·s_e + wb·b_e: two products, one sum.  ws, wb: finite and >= 0.
+ *   choice          the e with the largest score_e, the smallest e among equals; a NaN score never wins.  −1 if count
+ *                   is 0 or every score is NaN: such a tile takes the main light (lu0, lv0), finite; any other tile
+ *                   takes (lu_e, lv_e) of its choice, in fp64.
+ *   smoothing       smooth in [0, 8] passes of the 3x3 binomial (1 2 1)x(1 2 1) over the tile grid, per component:
+ *                   acc = 0, wsum = 0; for dy = −1..1 (outer), dx = −1..1 (inner), tiles outside the grid skipped:
+ *                   acc = acc + wt·f, wsum = wsum + wt with wt = (2 − |dy|)·(2 − |dx|); the result is acc/wsum.
+ *                   Intermediates stay fp64 in the workspace.
+ *   field           device fp32 [Ty][Tx][2], rounded once from the last pass (or from the choice when smooth = 0).
+ *   choice          NULL or device int32 [Ty][Tx].
+ *   workspace       device, 8-byte aligned, workspace_bytes >= rti_light_field_workspace_bytes(Ty, Tx) = 32·Ty·Tx (0 on
+ *                   bad sizes); it need not be initialised.
+ * rti_relight_field (a light per pixel; one launch, a pixel per lane):
+ *   light_form RTI_LIGHT_TILES   light: device fp32 [Ty][Tx][2] for tile edge T.  Per pixel (x, y) in fp64:
+ *                   fx = ((double)x − (double)(T − 1)/2)/(double)T clamped to [0, Tx − 1]; i0 = floor(fx),
+ *                   i1 = min(i0 + 1, Tx − 1), a = fx − i0; fy, j0, j1, b likewise along y with Ty.  Per component:
+ *                   top = f[j0][i0] + a·(f[j0][i1] − f[j0][i0]), bottom likewise on row j1,
+ *                   l = top + b·(bottom − top).  The light is ((float)lu, (float)lv).
+ *   light_form RTI_LIGHT_PIXELS  light: device fp32 [H·W][2], used as it is; T is not read.  The entry for any other
+ *                   source of per-pixel light directions, e.g. a near-light correction.
+ *   value           per channel c: rti_relight's F32 value of that channel's own coefficients at the pixel's light,
+ *                   bit for bit: basis_eval<float>(lu, lv) on the device, acc = c_0·b_0, acc = fmaf(c_j, b_j, acc);
+ *                   that is rti_relight(coef_c, (double)lu, (double)lv) at that pixel.  A light with a non-finite
+ *                   component gives NaN instead.  Converted once: F32, or I32 / U8 as rti_relight (NaN gives INT32_MIN
+ *                   and 0).
+ *   out             [p] for C = 1, [p][c] for C = 3.  4·C·k + 8 bytes (PIXELS) in and C·sizeof(out) out per pixel.
+ *   Lane map, fast paths and alignment rules of the maps and the output: rti_relight_hsh_specular's for one direction;
+ *   anything they cannot serve, and the last partial wave, loads and stores per lane and gives the same bits.
+ * All: device pointers, stream-ordered, no allocation, no synchronisation, capturable in a hipGraph (the candidates,
+ * weights and main light are then part of the capture).  Every argument check answers before any HIP call.
+ * RTI_ERR_BAD_ARG: a null pointer (w, count of rti_light_scores and choice may be null); H or W < 1 or H·W >= 2^31; Ty or
+ * Tx < 1; a tile edge other than 8, 16, 32; E outside [1, RTI_LIGHT_MAX_CANDIDATES]; a non-finite candidate, weight or
+ * main light; ws or wb negative or not finite; smooth outside [0, 8]; C other than 1 or 3; a bad coefficient layout or
+ * light form; a channel stride below dense (C = 3); scores or workspace off 8 bytes, light off 4; a workspace too
+ * small.  RTI_ERR_UNSUPPORTED: an unknown basis; an out_dtype other than F32 / I32 / U8.
+ * Not built: the 8-bit and LRGB forms, a multi-GPU wrapper, the enhanced modes (diffuse gain, specular) under a light
+ * field, overlapping tiles, fp64 maps. */
+#define RTI_LIGHT_MAX_CANDIDATES 64
+#define RTI_LIGHT_TILES  0   /* light[Ty][Tx][2], bilinear between the tile centres */
+#define RTI_LIGHT_PIXELS 1   /* light[H*W][2] */
+int    rti_light_scores(const float* coef, int basis, int coef_layout, int C, int64_t coef_channel_stride,
+                        int H, int W, int T, const float* w /* HOST, NULL ok */,
+                        const double* luv /* HOST [E][2] */, int E,
+                        double* scores, int32_t* count /* NULL ok */, rti_stream_t stream);
+size_t rti_light_field_workspace_bytes(int Ty, int Tx);
+int    rti_light_field(const double* scores, const int32_t* count, int Ty, int Tx,
+                       const double* luv /* HOST [E][2] */, int E, double ws, double wb, double lu0, double lv0,
+                       int smooth, void* workspace, size_t workspace_bytes,
+                       float* field, int32_t* choice /* NULL ok */, rti_stream_t stream);
+int    rti_relight_field(const float* coef, int basis, int coef_layout, int C, int64_t coef_channel_stride,
+                         int H, int W, const float* light, int light_form, int T,
+                         void* out, int out_dtype, rti_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -53,6 +53,8 @@ bara96/Smartphone-based-RTI: analysis.py:196-411, interactive_relighting.py:11-3
     n, albedo = rti.photometric_stereo(I, lu, lv)    # normals to geometry: the least-squares height map, on the GPU
     z = rti.height_from_normals(n)                   # [H, W] in pixel units, zero mean, NaN where the normal is unusable
 
+    img = rti.relight_multilight(coef, 0.3, -0.2)    # multi-light detail enhancement: each tile under its best light
+
 Compute runs in HIP kernels of librti.so (include/rti.h); importing this
 package does not touch the GPU.
 """
@@ -78,7 +80,9 @@ from .api import (BASES, FitAccumulator, apply_operator, basis_eval, basis_id, b
                   rgb_normals_into,
                   relight_hsh_specular, relight_hsh_specular_into, relight_hsh8_specular, relight_hsh8_specular_into,
                   relight_hsh_gain, relight_hsh_gain_into, relight_hsh8_gain, relight_hsh8_gain_into,
-                  height_from_normals, height_from_normals_into, height_levels, height_workspace)
+                  height_from_normals, height_from_normals_into, height_levels, height_workspace,
+                  light_candidates, light_scores, light_scores_into, light_field, light_field_into,
+                  light_field_workspace, relight_field, relight_field_into, relight_multilight)
 from .io import read_ptm, read_ptm8, read_rti, write_ptm, write_rti
 
 __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_into", "fit_chunked",
@@ -104,7 +108,9 @@ __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_in
            "relight_hsh_specular", "relight_hsh_specular_into", "relight_hsh8_specular",
            "relight_hsh8_specular_into", "relight_hsh_gain", "relight_hsh_gain_into", "relight_hsh8_gain",
            "relight_hsh8_gain_into", "height_from_normals", "height_from_normals_into", "height_levels",
-           "height_workspace", "read_ptm", "read_ptm8", "write_ptm",
+           "height_workspace", "light_candidates", "light_scores", "light_scores_into", "light_field",
+           "light_field_into", "light_field_workspace", "relight_field", "relight_field_into", "relight_multilight",
+           "read_ptm", "read_ptm8", "write_ptm",
            "read_rti", "write_rti", "library_path", "load"]
 
 __version__ = "0.1.0"

@@ -43,6 +43,9 @@ RTI_UNSHARP_MAX_RADIUS = 32  # rti_map_unsharp: the largest Gaussian radius
 RTI_SPECULAR_MAX_DIRS = 16  # rti_relight_hsh_specular, rti_relight_hsh_gain: the most directions of a launch
 RTI_HEIGHT_MULTIGRID = 0  # rti_height_from_normals preconditioners
 RTI_HEIGHT_JACOBI = 1
+RTI_LIGHT_MAX_CANDIDATES = 64  # rti_light_scores, rti_light_field: the most candidate lights of a call
+RTI_LIGHT_TILES = 0  # rti_relight_field light forms: a tile field [Ty][Tx][2]
+RTI_LIGHT_PIXELS = 1  # a light per pixel [H*W][2]
 
 RTI_KERNEL_AUTO = 0
 RTI_KERNEL_VALU = 1
@@ -221,6 +224,14 @@ SIGNATURES = {
     "rti_height_from_normals": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_double, _c_int, _c_void_p, _c_double,
                                          _c_int, _c_int, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_double_p,
                                          _c_void_p]),
+    "rti_light_scores": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_int, _c_int, _c_float_p,
+                                  _c_double_p, _c_int, _c_void_p, _c_void_p, _c_void_p]),
+    "rti_light_field_workspace_bytes": (ctypes.c_size_t, [_c_int, _c_int]),
+    "rti_light_field": (_c_int, [_c_void_p, _c_void_p, _c_int, _c_int, _c_double_p, _c_int, _c_double, _c_double,
+                                 _c_double, _c_double, _c_int, _c_void_p, ctypes.c_size_t, _c_void_p, _c_void_p,
+                                 _c_void_p]),
+    "rti_relight_field": (_c_int, [_c_void_p, _c_int, _c_int, _c_int, _c_i64, _c_int, _c_int, _c_void_p, _c_int,
+                                   _c_int, _c_void_p, _c_int, _c_void_p]),
 }
 
 _lock = threading.Lock()

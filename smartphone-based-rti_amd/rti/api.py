@@ -2755,6 +2755,249 @@ def height_from_normals(n, nz_min=0.1, flip_y=False, rtol=1e-6, max_iters=2000, 
     return (height, valid) if return_valid else height
 
 
+# ---- multi-light detail enhancement (rti_multilight.hip) ----------------------
+
+LIGHT_TILES = (8, 16, 32)
+
+
+def light_candidates(lu, lv, radius=0.3, rings=2, per_ring=8):
+    """The candidate lights of the multi-light search around the main light (lu, lv), on the host: fp64 [E, 2] with
+    E = 1 + rings·per_ring.  The main light comes first, then ring r = 1..rings at radius·r/rings with the angles
+    2πj/per_ring, j = 0..per_ring − 1.  A point outside the unit disc is scaled onto it."""
+    lu, lv, radius = float(lu), float(lv), float(radius)
+    rings, per_ring = int(rings), int(per_ring)
+    if not (np.isfinite(lu) and np.isfinite(lv) and np.isfinite(radius)) or radius < 0.0:
+        raise ValueError(f"lu, lv must be finite and radius finite and not negative; got {lu}, {lv}, {radius}")
+    if rings < 0 or per_ring < 1:
+        raise ValueError(f"rings must be >= 0 and per_ring >= 1; got {rings}, {per_ring}")
+    E = 1 + rings * per_ring
+    if E > L.RTI_LIGHT_MAX_CANDIDATES:
+        raise ValueError(f"at most {L.RTI_LIGHT_MAX_CANDIDATES} candidates; 1 + {rings}·{per_ring} = {E}")
+    pts = [(lu, lv)]
+    for r in range(1, rings + 1):
+        rad = radius * r / rings
+        for j in range(per_ring):
+            a = 2.0 * np.pi * j / per_ring
+            pts.append((lu + rad * np.cos(a), lv + rad * np.sin(a)))
+    out = np.array(pts, np.float64)
+    for i in range(E):
+        n = np.hypot(out[i, 0], out[i, 1])
+        if n > 1.0:
+            out[i] /= n
+        while out[i, 0] * out[i, 0] + out[i, 1] * out[i, 1] > 1.0:  # the division's rounding
+            out[i] *= 1.0 - 2.0 ** -52
+    return out
+
+
+def _tile_edge(tile):
+    if isinstance(tile, bool) or tile not in LIGHT_TILES:
+        raise ValueError(f"tile must be one of {LIGHT_TILES}; got {tile!r}")
+    return int(tile)
+
+
+def _tile_grid(H, W, T):
+    return (H + T - 1) // T, (W + T - 1) // T
+
+
+def _candidates_arg(luv):
+    """Candidate lights as light_candidates returns them -> host fp64 [E, 2], 1 <= E <= RTI_LIGHT_MAX_CANDIDATES."""
+    a = np.ascontiguousarray(np.asarray(luv.detach().cpu() if torch.is_tensor(luv) else luv, np.float64))
+    if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] < 1:
+        raise ValueError(f"luv must be [E, 2] with at least one candidate; got {a.shape}")
+    if a.shape[0] > L.RTI_LIGHT_MAX_CANDIDATES:
+        raise ValueError(f"at most {L.RTI_LIGHT_MAX_CANDIDATES} candidates per call; got {a.shape[0]}")
+    if not np.isfinite(a).all():
+        raise ValueError("luv must be finite")
+    return a
+
+
+def _image_maps(coef, b, cl):
+    """One CUDA fp32 map of an H x W image or three, contiguous or three contiguous maps a constant stride apart ->
+    (C, H, W, channel stride in elements or 0)."""
+    k = basis_terms(b)
+    if k < 0:
+        raise ValueError(f"unknown basis {b!r}")
+    _require_cuda(coef, "coef")
+    if coef.dtype != torch.float32:
+        raise ValueError(f"coef must be float32; got {coef.dtype}")
+    if coef.dim() == 4 and coef.shape[0] == 3:
+        one, C = coef[0], 3
+    elif coef.dim() == 3:
+        one, C = coef, 1
+    else:
+        raise ValueError("coef must be one map of an image, [H, W, k] (or [k, H, W] planar), or three, [3, ...]; got "
+                         f"{tuple(coef.shape)}")
+    H, W = _coef_spatial(one, k, cl)
+    if H < 1 or W < 1:
+        raise ValueError(f"the image must have at least one pixel; got {H}x{W}")
+    if coef.is_contiguous():
+        stride = 0
+    elif C == 3 and one.is_contiguous() and coef.stride(0) >= H * W * k:
+        stride = coef.stride(0)
+    else:
+        raise ValueError("coef must be contiguous, or three contiguous maps [3, ...] a constant stride apart")
+    return C, int(H), int(W), int(stride)
+
+
+def light_scores_into(coef, luv, scores, count=None, *, basis="ptm", tile=16, layout="pixel", weights=None):
+    """Launch ``rti_light_scores`` on preallocated tensors (no allocation, graph-capturable: the candidates travel as
+    kernel arguments and become part of a capture).
+
+    coef: CUDA fp32 [H, W, k] or [3, H, W, k] (layout="pixel"), [k, H, W] or [3, k, H, W] ("planar"); contiguous, or
+    three contiguous maps a constant stride apart.  luv: host [E, 2], E <= 64.  scores: float64 with Ty·Tx·E·2
+    elements ([Ty, Tx, E, 2]: sharpness, brightness); count: int32 [Ty, Tx] or None."""
+    b, cl, T = basis_id(basis), _layout_id(layout), _tile_edge(tile)
+    cand = _candidates_arg(luv)
+    E = cand.shape[0]
+    C, H, W, stride = _image_maps(coef, b, cl)
+    Ty, Tx = _tile_grid(H, W, T)
+    st = L.lib().rti_light_scores(_vp(coef), b, cl, C, stride, H, W, T, _luma_weights(weights), _dptr(cand), E,
+                                  _map_out(scores, "scores", torch.float64, Ty * Tx * E * 2, coef),
+                                  None if count is None else _map_out(count, "count", torch.int32, Ty * Tx, coef),
+                                  _stream_of(coef))
+    L.check(st, "rti_light_scores")
+    return scores
+
+
+def light_scores(coef, luv, basis="ptm", *, tile=16, layout="pixel", weights=None):
+    """The multi-light search on the GPU in one launch (``rti_light_scores``): for every tile x tile block of the
+    image and every candidate light, the local sharpness (the mean squared difference of neighbouring pixels inside
+    the tile) and the brightness (the mean) of ``relight``'s float32 value of the luminance map, with no candidate
+    frame written to memory.  Pixels with a non-finite coefficient are left out.
+
+    coef: as ``light_scores_into``; luv: ``light_candidates(...)`` or any host [E, 2], E <= 64; tile 8, 16 or 32.
+    Returns (scores float64 [Ty, Tx, E, 2], count int32 [Ty, Tx], the usable pixels of each tile)."""
+    b, cl, T = basis_id(basis), _layout_id(layout), _tile_edge(tile)
+    E = _candidates_arg(luv).shape[0]
+    _, H, W, _ = _image_maps(coef, b, cl)
+    Ty, Tx = _tile_grid(H, W, T)
+    scores = torch.empty((Ty, Tx, E, 2), dtype=torch.float64, device=coef.device)
+    count = torch.empty((Ty, Tx), dtype=torch.int32, device=coef.device)
+    light_scores_into(coef, luv, scores, count, basis=b, tile=T, layout=cl, weights=weights)
+    return scores, count
+
+
+def light_field_workspace(Ty, Tx, device="cuda"):
+    """The device scratch of ``light_field_into`` for a Ty x Tx tile grid (``rti_light_field_workspace_bytes``)."""
+    nbytes = L.lib().rti_light_field_workspace_bytes(int(Ty), int(Tx))
+    if nbytes <= 0:
+        raise ValueError(f"Ty and Tx must be positive; got {Ty}x{Tx}")
+    return torch.empty(int(nbytes) // 8, dtype=torch.float64, device=device)
+
+
+def _field_scalars(lu, lv, ws, wb, smooth):
+    lu, lv, ws, wb = float(lu), float(lv), float(ws), float(wb)
+    if not (np.isfinite(lu) and np.isfinite(lv)):
+        raise ValueError(f"the main light must be finite; got ({lu}, {lv})")
+    if not (np.isfinite(ws) and np.isfinite(wb)) or ws < 0.0 or wb < 0.0:
+        raise ValueError(f"ws and wb must be finite and not negative; got {ws}, {wb}")
+    if isinstance(smooth, bool) or int(smooth) != smooth or not 0 <= smooth <= 8:
+        raise ValueError(f"smooth must be an integer in [0, 8]; got {smooth!r}")
+    return lu, lv, ws, wb, int(smooth)
+
+
+def light_field_into(scores, count, luv, workspace, field, choice=None, *, lu, lv, ws=1.0, wb=0.5, smooth=2):
+    """Launch ``rti_light_field`` on preallocated tensors (no allocation, graph-capturable; 1 + smooth launches).
+
+    scores: CUDA float64 [Ty, Tx, E, 2] and count: int32 [Ty, Tx] of ``light_scores``; luv: the same candidates;
+    workspace: ``light_field_workspace(Ty, Tx)``; field: float32 [Ty, Tx, 2]; choice: int32 [Ty, Tx] or None;
+    (lu, lv): the main light, taken by tiles without a usable pixel."""
+    _require_cuda(scores, "scores")
+    cand = _candidates_arg(luv)
+    E = cand.shape[0]
+    if scores.dtype != torch.float64 or scores.dim() != 4 or tuple(scores.shape[2:]) != (E, 2) \
+            or not scores.is_contiguous() or scores.numel() == 0:
+        raise ValueError(f"scores must be a contiguous float64 [Ty, Tx, {E}, 2] tensor; got {scores.dtype} "
+                         f"{tuple(scores.shape)}")
+    Ty, Tx = int(scores.shape[0]), int(scores.shape[1])
+    lu, lv, ws, wb, smooth = _field_scalars(lu, lv, ws, wb, smooth)
+    need = int(L.lib().rti_light_field_workspace_bytes(Ty, Tx))
+    wsp = _workspace_arg(workspace, need, scores)
+    st = L.lib().rti_light_field(_vp(scores), _map_out(count, "count", torch.int32, Ty * Tx, scores), Ty, Tx,
+                                 _dptr(cand), E, ws, wb, lu, lv, smooth, wsp,
+                                 workspace.numel() * workspace.element_size(),
+                                 _map_out(field, "field", torch.float32, Ty * Tx * 2, scores),
+                                 None if choice is None else _map_out(choice, "choice", torch.int32, Ty * Tx, scores),
+                                 _stream_of(scores))
+    L.check(st, "rti_light_field")
+    return field
+
+
+def light_field(scores, count, luv, lu, lv, *, ws=1.0, wb=0.5, smooth=2, return_choice=False):
+    """The light field of the multi-light mode on the GPU (``rti_light_field``): per tile the candidate with the
+    largest ws·sharpness + wb·brightness (each normalised by its largest value over the tile's candidates), a tile
+    without a usable pixel taking the main light (lu, lv), then ``smooth`` passes of the 3x3 binomial over the tile
+    grid.  Returns float32 [Ty, Tx, 2]; with return_choice also int32 [Ty, Tx] (−1: the main light)."""
+    _field_scalars(lu, lv, ws, wb, smooth)
+    _candidates_arg(luv)
+    _require_cuda(scores, "scores")
+    if scores.dim() != 4 or scores.numel() == 0:
+        raise ValueError(f"scores must be [Ty, Tx, E, 2]; got {tuple(scores.shape)}")
+    Ty, Tx = int(scores.shape[0]), int(scores.shape[1])
+    field = torch.empty((Ty, Tx, 2), dtype=torch.float32, device=scores.device)
+    choice = torch.empty((Ty, Tx), dtype=torch.int32, device=scores.device) if return_choice else None
+    light_field_into(scores.contiguous(), count.contiguous() if torch.is_tensor(count) else count, luv,
+                     light_field_workspace(Ty, Tx, scores.device), field, choice, lu=lu, lv=lv, ws=ws, wb=wb,
+                     smooth=smooth)
+    return (field, choice) if return_choice else field
+
+
+def relight_field_into(coef, light, out, *, basis="ptm", tile=None, layout="pixel"):
+    """Launch ``rti_relight_field`` on preallocated tensors (no allocation, graph-capturable).
+
+    coef: as ``light_scores_into``.  light: contiguous CUDA float32; with tile = 8, 16 or 32 a tile field
+    [Ty, Tx, 2], sampled bilinearly between the tile centres; with tile=None a light per pixel [H, W, 2].  out:
+    float32, int32 or uint8 with H·W elements for one map, H·W·3 ([H, W, 3]) for three."""
+    b, cl = basis_id(basis), _layout_id(layout)
+    T = 0 if tile is None else _tile_edge(tile)
+    C, H, W, stride = _image_maps(coef, b, cl)
+    n = H * W * 2 if tile is None else 2 * int(np.prod(_tile_grid(H, W, T)))
+    odt = _out8_dtype(out)
+    st = L.lib().rti_relight_field(_vp(coef), b, cl, C, stride, H, W, _map_out(light, "light", torch.float32, n, coef),
+                                   L.RTI_LIGHT_PIXELS if tile is None else L.RTI_LIGHT_TILES, T,
+                                   _map_out(out, "out", out.dtype, H * W * C, coef), odt, _stream_of(coef))
+    L.check(st, "rti_relight_field")
+    return out
+
+
+def relight_field(coef, light, basis="ptm", *, tile=None, layout="pixel", out_dtype=torch.float32):
+    """Relight under a light direction per pixel on the GPU in one launch (``rti_relight_field``): per channel
+    ``relight``'s float32 value at that pixel's own light, the basis evaluated per pixel on the device.
+
+    coef: CUDA fp32 [H, W, k] or [3, H, W, k] (planar: [k, H, W], [3, k, H, W]).  light: CUDA float32 [H, W, 2], a
+    direction per pixel (e.g. a near-light correction), or with tile = 8, 16 or 32 the tile field [Ty, Tx, 2] of
+    ``light_field``.  Returns [H, W] or [H, W, 3] in out_dtype: float32, or int32 / uint8 converted as ``relight``
+    does.  A pixel whose light is not finite is NaN (INT32_MIN, 0)."""
+    b, cl = basis_id(basis), _layout_id(layout)
+    T = 0 if tile is None else _tile_edge(tile)
+    if out_dtype not in _ENHANCED_DTYPES:
+        raise ValueError("out_dtype must be float32, int32 or uint8")
+    C, H, W, _ = _image_maps(coef, b, cl)
+    _require_cuda(light, "light")
+    want = (H, W, 2) if tile is None else _tile_grid(H, W, T) + (2,)
+    if light.dtype != torch.float32 or tuple(light.shape) != want:
+        raise ValueError(f"light must be float32 {list(want)}; got {light.dtype} {tuple(light.shape)}")
+    out = torch.empty((H, W) + ((3,) if C == 3 else ()), dtype=out_dtype, device=coef.device)
+    return relight_field_into(coef, light.contiguous(), out, basis=b, tile=tile, layout=cl)
+
+
+def relight_multilight(coef, lu, lv, basis="ptm", *, tile=16, radius=0.3, rings=2, per_ring=8, ws=1.0, wb=0.5,
+                       smooth=2, layout="pixel", out_dtype=torch.float32, return_field=False):
+    """Multi-light detail enhancement on the GPU (Palma et al. 2010; RTIViewer's multi-light mode): every tile of the
+    image is lit by the candidate around (lu, lv) that shows its relief best, the choices are smoothed into a light
+    field and the image is relit with a light per pixel.  ``light_candidates``, ``light_scores``, ``light_field`` and
+    ``relight_field(..., tile=tile)`` composed: 3 + smooth launches, no candidate frame in memory.
+
+    coef: CUDA fp32 [H, W, k] or [3, H, W, k] (planar: [k, H, W], [3, k, H, W]); the search runs on the luminance of
+    three maps, the relight on each channel.  Returns [H, W] or [H, W, 3] in out_dtype; with return_field also the
+    float32 field [Ty, Tx, 2] it used."""
+    luv = light_candidates(lu, lv, radius, rings, per_ring)
+    scores, count = light_scores(coef, luv, basis, tile=tile, layout=layout)
+    field = light_field(scores, count, luv, lu, lv, ws=ws, wb=wb, smooth=smooth)
+    out = relight_field(coef, field, basis, tile=tile, layout=layout, out_dtype=out_dtype)
+    return (out, field) if return_field else out
+
+
 # ---- light operators (RBF, fused PTM/HSH fit + evaluation) ----------------------------------
 
 def _query(qu, qv):

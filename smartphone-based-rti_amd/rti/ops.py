@@ -4,7 +4,8 @@
 ``lrgb_quantise`` / ``relight_lrgb8`` / ``hsh_quantise`` / ``relight_hsh8`` / ``hsh_normals`` / ``hsh8_normals`` /
 ``rgb8_quantise`` / ``relight_rgb8`` / ``rgb8_normals`` / ``relight_lrgb_enhanced`` / ``relight_lrgb8_enhanced`` /
 ``relight_rgb8_enhanced`` / ``relight_rgb`` / ``relight_rgb_enhanced`` / ``rgb_normals`` / ``relight_hsh_specular`` /
-``relight_hsh8_specular`` / ``relight_hsh_gain`` / ``relight_hsh8_gain`` / ``height_from_normals``.
+``relight_hsh8_specular`` / ``relight_hsh_gain`` / ``relight_hsh8_gain`` / ``height_from_normals`` / ``light_scores`` /
+``light_field`` / ``relight_field``.
 
 They let the fit and relight kernels sit inside torch programs (and
 ``torch.library`` fake-tensor tracing) while the compute stays in librti's
@@ -903,3 +904,70 @@ def height_from_normals(n: torch.Tensor, nz_min: float = 0.1, flip_y: bool = Fal
 @height_from_normals.register_fake
 def _(n, nz_min=0.1, flip_y=False, rtol=1e-6, max_iters=2000, jacobi=False, z0=None, planar=False, check_every=8):
     return n.new_empty(tuple(n.shape[1:]) if planar else tuple(n.shape[:2]))
+
+
+# ---- multi-light detail enhancement ------------------------------------------
+
+def _candidates(luv):
+    """luv [E, 2] on any device -> host fp64 [E, 2]: the candidates travel as kernel arguments."""
+    if luv.dim() != 2 or luv.shape[1] != 2:
+        raise ValueError(f"luv must be [E, 2]; got {tuple(luv.shape)}")
+    return luv.detach().cpu().double().numpy()
+
+
+def _image_dims(coef, planar):
+    """Maps [H, W, k] / [3, H, W, k] (or [k, H, W] / [3, k, H, W] if planar) -> (H, W)."""
+    return tuple(coef.shape[-2:]) if planar else tuple(coef.shape[-3:-1])
+
+
+@torch.library.custom_op("rti::light_scores", mutates_args=())
+def light_scores(coef: torch.Tensor, luv: torch.Tensor, basis: int = L.RTI_BASIS_PTM6, tile: int = 16,
+                 planar: bool = False, weights: Optional[Sequence[float]] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The multi-light search (``rti_light_scores``).  coef CUDA fp32 [H, W, k] or [3, H, W, k] (or [k, H, W] /
+    [3, k, H, W] if planar), luv [E, 2] with E <= 64 (read on the host), tile 8, 16 or 32 -> (scores fp64
+    [Ty, Tx, E, 2], count int32 [Ty, Tx])."""
+    api._require_cuda(coef, "coef")
+    return api.light_scores(coef.contiguous(), _candidates(luv), basis, tile=tile,
+                            layout="planar" if planar else "pixel", weights=weights)
+
+
+@light_scores.register_fake
+def _(coef, luv, basis=L.RTI_BASIS_PTM6, tile=16, planar=False, weights=None):
+    H, W = _image_dims(coef, planar)
+    Ty, Tx = (H + tile - 1) // tile, (W + tile - 1) // tile
+    return (coef.new_empty((Ty, Tx, luv.shape[0], 2), dtype=torch.float64),
+            coef.new_empty((Ty, Tx), dtype=torch.int32))
+
+
+@torch.library.custom_op("rti::light_field", mutates_args=())
+def light_field(scores: torch.Tensor, count: torch.Tensor, luv: torch.Tensor, lu: float, lv: float, ws: float = 1.0,
+                wb: float = 0.5, smooth: int = 2) -> torch.Tensor:
+    """The light field of the multi-light mode (``rti_light_field``).  scores fp64 [Ty, Tx, E, 2] and count int32
+    [Ty, Tx] of ``light_scores``, luv the same candidates, (lu, lv) the main light -> fp32 [Ty, Tx, 2]."""
+    api._require_cuda(scores, "scores")
+    api._require_cuda(count, "count")
+    _same_device(scores=scores, count=count)
+    return api.light_field(scores, count, _candidates(luv), lu, lv, ws=ws, wb=wb, smooth=smooth)
+
+
+@light_field.register_fake
+def _(scores, count, luv, lu, lv, ws=1.0, wb=0.5, smooth=2):
+    return scores.new_empty(tuple(scores.shape[:2]) + (2,), dtype=torch.float32)
+
+
+@torch.library.custom_op("rti::relight_field", mutates_args=())
+def relight_field(coef: torch.Tensor, light: torch.Tensor, basis: int = L.RTI_BASIS_PTM6, tile: int = 0,
+                  planar: bool = False, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """Relight under a light per pixel (``rti_relight_field``).  coef as ``light_scores``; light fp32 [H, W, 2]
+    (tile = 0) or the tile field [Ty, Tx, 2] of ``light_field`` (tile 8, 16 or 32) -> [H, W] or [H, W, 3] in
+    out_dtype (float32, int32 or uint8)."""
+    api._require_cuda(coef, "coef")
+    api._require_cuda(light, "light")
+    _same_device(coef=coef, light=light)
+    return api.relight_field(coef.contiguous(), light, basis, tile=tile if tile else None,
+                             layout="planar" if planar else "pixel", out_dtype=out_dtype)
+
+
+@relight_field.register_fake
+def _(coef, light, basis=L.RTI_BASIS_PTM6, tile=0, planar=False, out_dtype=torch.float32):
+    return coef.new_empty(_image_dims(coef, planar) + ((3,) if coef.dim() == 4 else ()), dtype=out_dtype)
