@@ -136,7 +136,8 @@ def _plans():
     farlight over 4-byte elements holds ONE channel: a second one must start at N·L >= 2^31 elements and end past
     2^32, which with the 2^31 elements in front of the base (the signed truncation of the first offset past 2^31)
     is 26 GiB, over the cap.  A single channel never uses its channel stride; farchan drives that.  uint8 stacks
-    keep two channels."""
+    keep two channels, and the three of photometric stereo (ps-farlight-es1: 20 planes 2^32/19 bytes apart per
+    channel, 14.4 GiB); its 4-byte farlight plans hold one channel for the same reason."""
     out = {}
 
     def add(p):
@@ -162,6 +163,16 @@ def _plans():
         add(row_plan(f"pm-farpixel-es4-N20-{v}", 4, P0, 20, v))  # P0 pixel rows of N samples, one channel (as farlight)
         for k in (6, 9, 16):  # 1076 = 1024 + 52: the ragged size of the map readers' path tests
             add(channel_plan(f"maps-farchan-k{k}-P1076-{v}", 4, 3, 1, 1076 * k, v))
+        for k in (6, 9, 16):  # 703 = 19 × 37: the multi-light image, 3 × 5 tiles of edge 8 ragged both ways
+            add(channel_plan(f"maps-farchan-k{k}-P703-{v}", 4, 3, 1, 703 * k, v))
+        # photometric stereo, N = 20 at P0.  farchan: three channels (4-byte: channel 1 past 2^32 bytes, channel 2 past
+        # 2^31 elements; uint8: 2^32 and 2^33), the uint8 planes 1328 = 83·16 apart so that every plane of the aligned
+        # variant starts on a 16-byte boundary and the tile is staged by 16-byte loads.  farlight: one channel of 4-byte
+        # elements (the memory argument above), three of uint8 (14.4 GiB).
+        add(channel_plan(f"ps-farchan-es4-N20-P{P0}-{v}", 4, 3, 20, P0, v))
+        add(channel_plan(f"ps-farchan-es1-N20-P{P0}-{v}", 1, 3, 20, P0, v, row_stride=_up(P0, 16)))
+        add(row_plan(f"ps-farlight-es4-N20-P{P0}-{v}", 4, 20, P0, v))
+        add(row_plan(f"ps-farlight-es1-N20-P{P0}-{v}", 1, 20, P0, v, C=3))
     return out
 
 

@@ -22,7 +22,17 @@ Left out on purpose: launch generations under far strides (they need millions of
 and the padded-channel generation tests of test_gpu_strides.py stand for them), and anything that needs P·k
 itself past 2^31.  farlight over fp32 / int32 stacks and the far pixel_stride of rti_fit_shared_pm hold one
 channel (two go over the memory cap, far_ref._plans), so a second channel together with a far light stride is
-driven on uint8 stacks only."""
+driven on uint8 stacks only.
+
+The entries added since (the last three sections) run on the helpers of tests/test_gpu_map_strides.py, which holds
+their near forms: rti_relight_hsh_gain / rti_relight_hsh_specular and rti_light_scores / rti_relight_field over three
+fp32 maps a far coef_channel_stride apart (channel 1 past 2^32 bytes, channel 2 past 2^31 elements), and
+rti_photometric_stereo with a far channel_stride (three channels) or a far light_stride (one channel of fp32 / int32,
+three of uint8), each under (a), (b) at the check of the entry's dense test and (c) in both variants: those entries
+state the same bits on every path.  Their outputs are dense.  Left out there on purpose: outputs of these entries have
+no stride arguments, so an output offset past 2^31 needs E·P·C or P·k itself past 2^31, the workload's own sizes,
+which test_gpu_fullsize.py stands for; and the 8-bit payload entries (rti_relight_hsh8_gain, rti_relight_hsh8_specular)
+take no strides at all."""
 import ctypes
 import functools
 
@@ -34,6 +44,7 @@ import far_ref as fr
 import rti
 import rti_oracle as o
 import stride_ref as sr
+import test_gpu_map_strides as tn
 import test_gpu_strides as ts
 from conftest import coef_close, relight_close
 from rti import _lib as L
@@ -683,3 +694,65 @@ def test_rgb8_qparams_quantise(cuda, variant):
         assert not torch.isnan(outs[1][0]).any()
         for name, a, d in zip(("qparams", "coef8"), *outs):
             assert same_bytes(a, d), (f"rgb8 {name}", layout, variant, "differs from the dense call")
+
+
+# ---- renderers under a normal map, multi-light and photometric stereo (helpers: tests/test_gpu_map_strides.py) ------
+assert tn.PM == PM and tn.PS_P == P0
+LAYOUT_IDS = [name for name, _ in ts.LAYOUTS]
+
+
+@pytest.mark.parametrize("variant", fr.VARIANTS)
+@pytest.mark.parametrize("layout,lid", ts.LAYOUTS, ids=LAYOUT_IDS)
+@pytest.mark.parametrize("k", [9, 16])
+def test_render_far_channel_stride(cuda, k, layout, lid, variant):
+    """rti_relight_hsh_gain and rti_relight_hsh_specular over three far maps (gain 2.5; kd 0.4, ks 150, exponent 75),
+    pixel-major normals (the layout that stages), E = 3, F32 and U8: the restatements at their dense tests' check, and
+    the bits of the dense call in both variants (the odd stride reads one element per lane)."""
+    flat = tn.flat_maps(tn.G.maps(PM, k, "fp32"), layout)
+    far = FarIn(cuda, f"maps-farchan-k{k}-P{PM}-{variant}", flat[:, None, :], "f32")
+    dense = tn.Maps(cuda, flat, None)
+    nid = L.RTI_NORMAL_PIXEL_MAJOR
+    for entry in sorted(tn.RENDER):
+        n = tn.normal_map(cuda, tn.RENDER[entry][0].normals(PM), "pixel", None)
+        for dt in ("f32", "u8"):
+            what = f"rti_relight_hsh_{entry} k={k} {layout} {dt} farchan {variant}"
+            got = tn.render(cuda, entry, far.ptr, far.cs, lid, k, 3, PM, n.ptr, nid, dt, what)
+            worst = tn.check_render(entry, got, PM, k, 3, dt, what)
+            print(f"{what}: worst fp32 error {worst:.3g} of its bound")
+            want = tn.render(cuda, entry, dense.ptr, 0, lid, k, 3, PM, n.ptr, nid, dt, what + " dense")
+            assert np.array_equal(got.view(np.uint8), want.view(np.uint8)), (what, "differs from the dense call")
+    del far
+
+
+@pytest.mark.parametrize("variant", fr.VARIANTS)
+@pytest.mark.parametrize("layout,lid", ts.LAYOUTS, ids=LAYOUT_IDS)
+@pytest.mark.parametrize("k", [6, 9, 16])
+def test_multilight_far_channel_stride(cuda, k, layout, lid, variant):
+    """rti_light_scores (scores within the header's bound of multilight_ref, count exact) and rti_relight_field under
+    a tile field (F32 and U8, equal to the restatement) over three far maps of 19 x 37 pixels, T = 8; every output
+    bit-equal to the dense call."""
+    flat = tn.flat_maps(tn.M.image_maps(*tn.HW, k, 3), layout)
+    far = FarIn(cuda, f"maps-farchan-k{k}-P{tn.HW[0] * tn.HW[1]}-{variant}", flat[:, None, :], "f32")
+    dense = tn.Maps(cuda, flat, None)
+    what = f"multi-light k={k} {layout} farchan {variant}"
+    worst = tn.check_multilight(cuda, k, layout, lid, (far.ptr, far.cs), (dense.ptr, 0), what, field_forms=(True,))
+    print(f"{what}: worst score error {worst:.3f} of its bound")
+    del far
+
+
+@pytest.mark.parametrize("variant", fr.VARIANTS)
+@pytest.mark.parametrize("dt,poison", tn.PS_DTYPES, ids=[d for d, _ in tn.PS_DTYPES])
+@pytest.mark.parametrize("form", ["farchan", "farlight"])
+def test_photometric_stereo(cuda, form, dt, poison, variant):
+    """rti_photometric_stereo, N = 20, P = 1316, with a far channel_stride (C = 3) or a far light_stride (C = 1 for
+    fp32 / int32: two such channels go over the memory cap, far_ref._plans; C = 3 for uint8): iters 0 and 2, both
+    normal layouts, the six outputs against ps_ref at test_gpu_ps.check's tolerances and bit-equal to the dense call,
+    kept exact against both.  The streaming form and the resident form of 256 pixels both run; the aligned variant
+    stages the tile by 16-byte loads, the odd one by elements."""
+    es = fr.ES[dt]
+    C = 1 if form == "farlight" and es == 4 else 3
+    i = FarIn(cuda, f"ps-{form}-es{es}-N{tn.PS_N}-P{P0}-{variant}", tn.ps_stack(dt, C), dt, poison)
+    assert tn.ps_vec(i.ptr.value, i.ls, i.cs, es, C) == (variant == "aligned")
+    tiles = tn.check_ps(cuda, i.ptr, dt, C, i.ls, i.cs, f"rti_photometric_stereo {form} C={C} {dt} {variant}")
+    assert tiles == {0, 256}, tiles
+    del i

@@ -228,7 +228,7 @@ def test_lights_per_pixel_are_the_diagonal_of_relight(cuda, basis):
             assert (np.isnan(got[bad]) if dt == torch.float32 else got[bad] == blank).all(), (layout, dt)
 
 
-def test_a_far_channel_stride_gives_the_same_bits(cuda):
+def test_a_padded_channel_stride_gives_the_same_bits(cuda):
     H, W, T, basis = 19, 37, 8, "hsh9"
     P, k = H * W, 9
     m = image_maps(H, W, k, 3)
