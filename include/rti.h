@@ -338,8 +338,8 @@ int rti_fit_shared_robust_plan(int k, int N, int in_dtype, int iters, int kernel
  * RESIDENT (iters > 0) copies a workgroup's tile [C][N][TP] into LDS once, by 16-byte loads when every plane
  * of the tile is 16-byte aligned; TP = the largest of 256 / 128 / 64 with C·N·TP·sizeof(element) <= 160 KiB.
  * rti_photometric_stereo_plan returns TP, or 0 for the streaming form.
- * Not built: pixel-major stacks, per-pixel light directions, fp64 stacks, a chunked (FitAccumulator) form
- * (the window needs the samples), a multi-GPU split. */
+ * Not built: pixel-major stacks, fp64 stacks, a chunked (FitAccumulator) form (the window needs the samples),
+ * a multi-GPU split.  (Per-pixel light directions: rti_photometric_stereo_near, below.) */
 int rti_ps_design(const float* lu, const float* lv, int n, double* A);
 int rti_photometric_stereo_plan(int N, int in_dtype, int C, int iters, int kernel);
 int rti_photometric_stereo(const double* A, int N, const void* I, int in_dtype, int64_t P, int C,
@@ -348,6 +348,49 @@ int rti_photometric_stereo(const double* A, int N, const void* I, int in_dtype, 
                            const float* w, float* normals, int normal_layout, float* albedo,
                            uint8_t* kind, float* res, int32_t* kept, int* fallback_px,
                            int kernel, rti_stream_t stream);
+
+/* ---- device: near-light photometric stereo (rti_ps_near.hip) ------------------------------
+ * rti_photometric_stereo for lights a few image widths from the object (the reference's phone flash): the
+ * direction to a light and, by the inverse square of the distance, its strength differ from pixel to pixel, so
+ * every pixel has its own design row per light, formed from the light's position and the pixel's, as
+ * compute_intensities / rti_light_dirs form cam_n − (x0+x, y0+y, 0).
+ *
+ * The fit, the tail (normal, albedo, kind 0 / 1 / 2 / 4), the outputs and their layouts, the argument checks
+ * and the streaming and LDS-resident forms with their plan rule are rti_photometric_stereo's, word for word;
+ * only the row a_n of light n differs.  For pixel p = y·W + x (x the column), in fp64:
+ *   pos   = (x0 + x, y0 + y, z_offset + h),  h = height[p] if height is given and that value is finite, else 0
+ *   d     = L_n − pos                                    (L_n = lights[n][0..2], one rounding per component)
+ *   s     = fma(d_x, d_x, fma(d_y, d_y, d_z·d_z))        (= r²)
+ *   y     = 1/√s to within 1 ulp (the fp64 reciprocal-square-root seed and two Newton steps,
+ *           y ← fma(y, fma(−(½s·y), y, ½), y))
+ *   falloff == 0:  f = s_n·y                 a_n = f·d   (= s_n·d/r: direction only)
+ *   falloff == 1:  f = ((s_n·y)·r0²)·(y·y)   a_n = f·d   (= s_n·(r0²/r²)·d/r: inverse square)
+ * s_n = lights[n][3] is the light's scale and r0 a reference distance (r0² is rounded once on the host), so a
+ * light of scale 1 at distance r0 has strength 1 and the albedo stays in intensity units.  Each component of
+ * a_n is within 6·2⁻⁵³ (falloff 0) or 16·2⁻⁵³ (falloff 1: 8 ulps) relative of the expression on the right
+ * evaluated exactly from the fp64 d: 3·2⁻⁵³ from s, 2·2⁻⁵³ from y, and one rounding per product.
+ * s == 0 (a light on the pixel) or a non-finite light gives y = NaN and a NaN row; the pixel then fails both
+ * solves of the fit like any singular system and ends as kind 4 (NaN normal and albedo, kept = N, counted in
+ * fallback_px); no branch skips its work.  The rows are formed anew in every pass (window, fallback, each Huber
+ * pass, the residual pass) by one device function, so every pass and both forms see the same bits; none is
+ * stored.  height_from_normals gives a zero-mean height: z_offset is the gauge and the caller's.
+ * lights: device fp64 [N][4] = x, y, z, scale, in the frame of rti_light_dirs' cams (pixel units).  height:
+ * device fp32 [H·W] or NULL.  I, in_dtype, C, the strides and every argument from lo on as
+ * rti_photometric_stereo, with P = H·W.
+ * Every argument check answers before any HIP call.  RTI_ERR_BAD_ARG, besides rti_photometric_stereo's cases
+ * (null lights in place of null A): H or W < 1, or H·W >= 2^31; falloff outside {0, 1}; r0 not finite or <= 0
+ * with falloff == 1 (it is not read otherwise); a non-finite x0, y0 or z_offset.
+ * rti_photometric_stereo_near_plan is rti_photometric_stereo_plan's rule.
+ * Not built: anisotropic (cos^μ) sources, perspective cameras, a per-component height gauge, pixel-major or
+ * fp64 stacks, a multi-GPU split. */
+int rti_photometric_stereo_near_plan(int N, int in_dtype, int C, int iters, int kernel);
+int rti_photometric_stereo_near(const double* lights, int N, const void* I, int in_dtype, int H, int W, int C,
+                                int64_t light_stride, int64_t channel_stride, double x0, double y0,
+                                const float* height, double z_offset, int falloff, double r0,
+                                float lo, float hi, int min_lights, int iters, float delta,
+                                const float* w, float* normals, int normal_layout, float* albedo,
+                                uint8_t* kind, float* res, int32_t* kept, int* fallback_px,
+                                int kernel, rti_stream_t stream);
 
 /* ---- device: the shared fit fed in chunks of light planes (rti_fit_accum.hip) -----------
  * rti_fit_shared_residual's per-pixel sums kept in HBM between calls, for stacks that do not fit beside

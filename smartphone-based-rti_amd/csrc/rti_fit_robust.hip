@@ -71,7 +71,7 @@ fit_robust_k(const double* __restrict__ A, int N, const T* __restrict__ I, int64
   }
 
   double c[K];
-  const RbOut o = rb_pixel<K, ITER>(A, N, y_of, lo, hi, min_lights, iters, delta, c);
+  const RbOut o = rb_pixel<K, ITER>(RbSharedRows<K>{A}, N, y_of, lo, hi, min_lights, iters, delta, c);
 
   if (live) {
     float* __restrict__ dst = coef + (int64_t)blockIdx.y * ocstride;

@@ -1,8 +1,12 @@
-// rti_robust_px.h -- the per-pixel robust fit shared by rti_fit_robust.hip (k = 6, 9: coefficients) and rti_ps.hip
-// (k = 3: photometric stereo): intensity window, Cholesky solve with the 1e-10·max diag G pivot rule, fallback to
-// every light, Huber IRLS (include/rti.h states the semantics).  One lane owns one pixel; the rows of A are
-// wave-uniform (scalar loads) and the fp64 state is k(k+1)/2 + k + 1 accumulators, factored in registers like
-// rti_perpixel.hip's ne_solve.  Both files run these templates as they stand, so a fit at a k has one arithmetic.
+// rti_robust_px.h -- the per-pixel robust fit shared by rti_fit_robust.hip (k = 6, 9: coefficients), rti_ps.hip and
+// rti_ps_near.hip (k = 3: photometric stereo): intensity window, Cholesky solve with the 1e-10·max diag G pivot rule,
+// fallback to every light, Huber IRLS (include/rti.h states the semantics).  One lane owns one pixel and the fp64
+// state is k(k+1)/2 + k + 1 accumulators, factored in registers like rti_perpixel.hip's ne_solve.  Every file runs
+// these templates as they stand, so a fit at a k has one arithmetic.
+//
+// The design row of light n comes from a row source R: a functor `void operator()(int n, double (&a)[K]) const`
+// called once per sample in every pass.  RbSharedRows reads the wave-uniform row A[n] (scalar loads, the values
+// stay in SGPR pairs); rti_ps_px.h's near-light source forms a lane-private row from the light and the pixel.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -41,11 +45,22 @@ struct RbSamples {
   __device__ __forceinline__ double operator()(int n) const { return (double)p[(int64_t)n * step]; }
 };
 
+// The shared design: row n of A [N][K], the same for every lane.
+template <int K>
+struct RbSharedRows {
+  const double* __restrict__ A;
+  __device__ __forceinline__ void operator()(int n, double (&a)[K]) const {
+    const double* An = A + (int64_t)n * K;  // wave-uniform row -> SGPR pairs
+#pragma unroll
+    for (int i = 0; i < K; ++i) a[i] = An[i];
+  }
+};
+
 enum { RB_W_WINDOW = 0, RB_W_ALL = 1, RB_W_HUBER = 2 };
 
 // sample weight: the window (or 1 for every light on a fallback pixel) times Huber's weight of the residual
 template <int K, int MODE>
-__device__ __forceinline__ double rb_weight(const double* __restrict__ An, double y, double lo, double hi, bool all,
+__device__ __forceinline__ double rb_weight(const double (&An)[K], double y, double lo, double hi, bool all,
                                             const double (&c)[K], double delta) {
   const double win = (all || (y >= lo && y <= hi)) ? 1.0 : 0.0;
   if constexpr (MODE == RB_W_ALL) return 1.0;
@@ -58,9 +73,9 @@ __device__ __forceinline__ double rb_weight(const double* __restrict__ An, doubl
 }
 
 // one pass over the pixel's N samples: G, b, q and the count of samples in the window
-template <int K, int MODE, bool NEED_Q, typename S>
-__device__ __forceinline__ void rb_accumulate(const double* __restrict__ A, int N, const S& y_of, double lo, double hi,
-                                              bool all, const double (&c)[K], double delta, RbSys<K>& s) {
+template <int K, int MODE, bool NEED_Q, typename R, typename S>
+__device__ __forceinline__ void rb_accumulate(const R& row_of, int N, const S& y_of, double lo, double hi, bool all,
+                                              const double (&c)[K], double delta, RbSys<K>& s) {
 #pragma unroll
   for (int i = 0; i < K * (K + 1) / 2; ++i) s.g[i] = 0.0;
 #pragma unroll
@@ -69,7 +84,8 @@ __device__ __forceinline__ void rb_accumulate(const double* __restrict__ A, int 
   int m = 0;
 #pragma unroll 2
   for (int n = 0; n < N; ++n) {
-    const double* An = A + (int64_t)n * K;  // wave-uniform row -> SGPR pairs
+    double An[K];
+    row_of(n, An);
     const double y = y_of(n);
     const double w = rb_weight<K, MODE>(An, y, lo, hi, all, c, delta);
     if constexpr (MODE == RB_W_WINDOW) m += w != 0.0 ? 1 : 0;
@@ -142,19 +158,19 @@ struct RbOut {
 };
 
 // The whole fit of one pixel from its samples (either form).  ITER: iters > 0.
-template <int K, bool ITER, typename S>
-__device__ __forceinline__ RbOut rb_pixel(const double* __restrict__ A, int N, const S& y_of, double lo, double hi,
-                                          int min_lights, int iters, double delta, double (&c)[K]) {
+template <int K, bool ITER, typename R, typename S>
+__device__ __forceinline__ RbOut rb_pixel(const R& row_of, int N, const S& y_of, double lo, double hi, int min_lights,
+                                          int iters, double delta, double (&c)[K]) {
   RbSys<K> s;
 #pragma unroll
   for (int i = 0; i < K; ++i) c[i] = __builtin_nan("");
-  rb_accumulate<K, RB_W_WINDOW, !ITER>(A, N, y_of, lo, hi, false, c, delta, s);
+  rb_accumulate<K, RB_W_WINDOW, !ITER>(row_of, N, y_of, lo, hi, false, c, delta, s);
   RbOut o;
   o.m = s.m;
   bool ok = s.m >= min_lights && rb_solve<K>(s, c);
   o.fell = !ok;
   if (!ok) {  // every light; a second failure leaves the NaN
-    rb_accumulate<K, RB_W_ALL, !ITER>(A, N, y_of, lo, hi, true, c, delta, s);
+    rb_accumulate<K, RB_W_ALL, !ITER>(row_of, N, y_of, lo, hi, true, c, delta, s);
     o.m = N;
     ok = rb_solve<K>(s, c);
   }
@@ -171,13 +187,14 @@ __device__ __forceinline__ RbOut rb_pixel(const double* __restrict__ A, int N, c
     o.ss = e < 0.0 ? 0.0 : e;  // rounding can leave an exact fit below zero; NaN passes
   } else {
     for (int t = 0; t < iters && ok; ++t) {
-      rb_accumulate<K, RB_W_HUBER, false>(A, N, y_of, lo, hi, o.fell, c, delta, s);
+      rb_accumulate<K, RB_W_HUBER, false>(row_of, N, y_of, lo, hi, o.fell, c, delta, s);
       ok = rb_solve<K>(s, c);  // a failed solve keeps the previous coefficients and stops
     }
     double e = 0.0;
 #pragma unroll 2
     for (int n = 0; n < N; ++n) {
-      const double* An = A + (int64_t)n * K;
+      double An[K];
+      row_of(n, An);
       const double y = y_of(n);
       double r = y;
 #pragma unroll

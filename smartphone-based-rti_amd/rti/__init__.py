@@ -6,6 +6,7 @@ bara96/Smartphone-based-RTI: analysis.py:196-411, interactive_relighting.py:11-3
     img = rti.relight(coef, 0.3, -0.2)               # [H, W]
     coef, res, kept = rti.fit_robust(I, lu, lv, lo=1, hi=254, iters=3, delta=5.0)  # clipped samples left out
     n, albedo = rti.photometric_stereo(I, lu, lv, lo=1, hi=254)   # Lambertian normals [H, W, 3] from the stack itself
+    n, albedo = rti.photometric_stereo_near(I, cams, refine=2)    # the same for a light near the object: a row per pixel
 
     acc = rti.FitAccumulator((H, W))                 # planes fed as they arrive, or a stack larger than HBM
     for frame, u, v in frames: acc.add(frame, u, v)
@@ -61,7 +62,7 @@ package does not touch the GPU.
 from . import _lib
 from ._lib import RTIError, RTILibraryMissing
 from .api import (BASES, FitAccumulator, apply_operator, basis_eval, basis_id, basis_operator, basis_terms,
-                  design_matrix, fit, fit_accum_solve_into, fit_accumulate_into, fit_chunked, fit_residual, fit_robust, fit_robust_into, photometric_stereo, photometric_stereo_into, ps_design, fit_shared_into, fit_shared_residual_into, fit_with_residual,
+                  design_matrix, fit, fit_accum_solve_into, fit_accumulate_into, fit_chunked, fit_residual, fit_robust, fit_robust_into, photometric_stereo, photometric_stereo_into, ps_design, photometric_stereo_near, photometric_stereo_near_into, ps_near_lights, fit_shared_into, fit_shared_residual_into, fit_with_residual,
                   gram_inverse,
                   interpolate_rbf, interpolate_rbf_perpixel, light_dirs, lsq_factors, pinv, q8_operator, h16_operator, rbf_operator,
                   normals, ptm_normals_into, relight, relight_enhanced, relight_enhanced_into, relight_frame,
@@ -88,7 +89,8 @@ from .io import read_ptm, read_ptm8, read_rti, write_ptm, write_rti
 __all__ = ["BASES", "FitAccumulator", "fit_accum_solve_into", "fit_accumulate_into", "fit_chunked",
            "RTIError", "RTILibraryMissing", "apply_operator", "basis_eval", "basis_id", "basis_operator",
            "basis_terms", "design_matrix", "fit", "fit_residual", "fit_robust", "fit_robust_into", "photometric_stereo",
-           "photometric_stereo_into", "ps_design", "fit_shared_into",
+           "photometric_stereo_into", "ps_design", "photometric_stereo_near", "photometric_stereo_near_into",
+           "ps_near_lights", "fit_shared_into",
            "fit_shared_residual_into",
            "fit_with_residual", "gram_inverse", "interpolate_rbf", "interpolate_rbf_perpixel", "light_dirs",
            "lsq_factors", "pinv", "q8_operator", "h16_operator",

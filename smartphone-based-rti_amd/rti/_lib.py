@@ -134,6 +134,12 @@ SIGNATURES = {
                                         ctypes.c_float, ctypes.c_float, _c_int, _c_int, ctypes.c_float, _c_void_p,
                                         _c_void_p, _c_int, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                         _c_int, _c_void_p]),
+    "rti_photometric_stereo_near_plan": (_c_int, [_c_int, _c_int, _c_int, _c_int, _c_int]),
+    "rti_photometric_stereo_near": (_c_int, [_c_void_p, _c_int, _c_void_p, _c_int, _c_int, _c_int, _c_int, _c_i64, _c_i64,
+                                             ctypes.c_double, ctypes.c_double, _c_void_p, ctypes.c_double, _c_int,
+                                             ctypes.c_double, ctypes.c_float, ctypes.c_float, _c_int, _c_int,
+                                             ctypes.c_float, _c_void_p, _c_void_p, _c_int, _c_void_p, _c_void_p,
+                                             _c_void_p, _c_void_p, _c_void_p, _c_int, _c_void_p]),
     "rti_fit_accum_state_doubles": (_c_i64, [_c_int, _c_i64, _c_int]),
     "rti_fit_accumulate": (_c_int, [_c_void_p, _c_int, _c_int, _c_void_p, _c_int, _c_i64, _c_int, _c_i64, _c_i64,
                                     _c_void_p, _c_i64, _c_int, _c_void_p]),

@@ -756,6 +756,143 @@ def photometric_stereo(I, lu, lv, lz=None, *, lo=None, hi=None, min_lights=None,
     return tuple(out)
 
 
+def ps_near_lights(light_pos, light_scale=None):
+    """Host fp64 [N, 4] light table of near-light photometric stereo: the rows (x, y, z, scale) from positions
+    [N, 3] in the frame of ``light_dirs``' ``cams`` and the lights' relative strengths (default 1)."""
+    pos = np.asarray(light_pos.detach().cpu() if torch.is_tensor(light_pos) else light_pos, dtype=np.float64)
+    if pos.ndim != 2 or pos.shape[1] != 3:
+        raise ValueError(f"light_pos must be [N, 3]; got {pos.shape}")
+    lights = np.ones((pos.shape[0], 4), dtype=np.float64)
+    lights[:, :3] = pos
+    if light_scale is not None:
+        sc = np.asarray(light_scale.detach().cpu() if torch.is_tensor(light_scale) else light_scale, dtype=np.float64)
+        if sc.shape != (pos.shape[0],):
+            raise ValueError(f"light_scale must be [{pos.shape[0]}]; got {sc.shape}")
+        lights[:, 3] = sc
+    return lights
+
+
+def photometric_stereo_near_into(lights_dev, I3, H, W, normals, albedo, kind, res, kept, fallback, *, lo, hi,
+                                 min_lights, origin=(0.0, 0.0), height=None, z_offset=0.0, falloff=True, r0=1.0,
+                                 iters=0, delta=0.0, weights=None, normal_layout="pixel", kernel=0, light_stride=None):
+    """Launch ``rti_photometric_stereo_near`` on preallocated tensors (no allocation, graph-capturable).
+
+    lights_dev fp64 [N, 4] (``ps_near_lights`` on the device), I3 CUDA [C, N, H·W] light-major as
+    ``photometric_stereo_into`` takes it (``light_stride`` likewise); pixel p = y·W + x sits at (origin[0] + x,
+    origin[1] + y, z_offset + height[p]).  height: fp32 [H·W] (any shape of that many elements) or None = the
+    plane; a non-finite entry counts as 0.  falloff: inverse-square strength (r0/r)², r0 the distance at which a
+    light's scale is its strength; False = direction only.  The outputs and the remaining arguments as
+    ``photometric_stereo_into``."""
+    C, N, P = I3.shape
+    H, W = int(H), int(W)
+    if H * W != P:
+        raise ValueError(f"H·W = {H}·{W} is not the stack's {P} pixels")
+    ls = P if light_stride is None else int(light_stride)
+    if lights_dev.dtype != torch.float64 or tuple(lights_dev.shape) != (N, 4) or not lights_dev.is_contiguous():
+        raise ValueError(f"lights must be contiguous float64 [{N}, 4]; got {lights_dev.dtype} {tuple(lights_dev.shape)}")
+    _require_cuda(lights_dev, "lights")
+    if ls < P or any(n > 1 and s != w for n, s, w in zip(I3.shape, I3.stride(), (N * ls, ls, 1))):
+        raise ValueError(f"I3 strides {tuple(I3.stride())} are not light-major planes of stride {ls}")
+
+    def opt(t, name, dtype, n):
+        return None if t is None else _map_out(t, name, dtype, n, I3)
+
+    st = L.lib().rti_photometric_stereo_near(
+        _vp(lights_dev), N, _vp(I3), _IN_DTYPES[I3.dtype], H, W, C, ls, N * ls, float(origin[0]), float(origin[1]),
+        opt(height, "height", torch.float32, P), float(z_offset), int(bool(falloff)), float(r0), float(lo), float(hi),
+        int(min_lights), int(iters), float(delta), _luma_weights(weights),
+        _map_out(normals, "normals", torch.float32, 3 * P, I3), _normal_layout_id(normal_layout),
+        _map_out(albedo, "albedo", torch.float32, C * P, I3), opt(kind, "kind", torch.uint8, P),
+        opt(res, "res", torch.float32, C * P), opt(kept, "kept", torch.int32, C * P),
+        opt(fallback, "fallback", torch.int32, 1), int(kernel), _stream_of(I3))
+    L.check(st, "rti_photometric_stereo_near")
+
+
+def photometric_stereo_near(I, light_pos, *, light_scale=None, origin=(0.0, 0.0), height=None, z_offset=0.0,
+                            falloff=True, r0=None, refine=0, height_kw=None, return_height=False, lo=None, hi=None,
+                            min_lights=None, iters=0, delta=None, weights=None, normal_layout="pixel",
+                            return_kind=False, return_res=False, return_kept=False, stats=None, kernel=0):
+    """``photometric_stereo`` for lights near the object (``rti_photometric_stereo_near``): every pixel gets its own
+    light vector and strength from the light's position, l = s_n·(r0/r)²·d/r with d = light_pos_n − (origin[0] + x,
+    origin[1] + y, z_offset + height[y, x]) and r = ‖d‖, instead of one direction for the whole image.
+
+    I: CUDA [N, H, W] or [3, N, H, W] ([N, P] is one row of P pixels).  light_pos: [N, 3] in pixel units, in the
+    frame of ``light_dirs``' ``cams`` (the reference pipeline's camera positions feed it as they are); light_scale:
+    None or [N] relative strengths.  height: None (the plane z = z_offset) or fp32 [H, W] above z_offset; NaN
+    counts as 0.  falloff=False keeps the direction only.  r0: the distance at which a light's scale is its
+    strength, so the albedo stays in intensity units; default the lights' mean distance from the image centre at z =
+    z_offset.  refine=K runs K rounds of normals -> ``height_from_normals(n, **height_kw)`` -> the same launch with
+    that height; the height it returns has zero mean, so z_offset is the gauge and the caller's.  The workspace and
+    the outputs are allocated once.  The robust arguments and the returns are ``photometric_stereo``'s, then with
+    return_height the last height map used, fp32 [H, W] (zeros if none was)."""
+    _require_cuda(I, "I")
+    if I.dtype not in _IN_DTYPES:
+        raise ValueError(f"I dtype {I.dtype} unsupported (float32, uint8 or int32)")
+    nl = _normal_layout_id(normal_layout)
+    C, N, P, spatial = _stack_shape(I)
+    H, W = (1, P) if len(spatial) == 1 else spatial
+    if C not in (1, 3):
+        raise ValueError(f"a 4-D stack must be RGB, [3, N, H, W]; got {C} channels")
+    if N < 3:
+        raise ValueError(f"shapes not aligned: {N} lights < 3 unknowns")
+    lights = ps_near_lights(light_pos, light_scale)
+    if lights.shape[0] != N:
+        raise ValueError(f"{lights.shape[0]} light positions for {N} intensity planes")
+    refine = int(refine)
+    if refine < 0:
+        raise ValueError("refine must be >= 0")
+    x0, y0, z_offset = float(origin[0]), float(origin[1]), float(z_offset)
+    if r0 is None:
+        centre = np.array([x0 + 0.5 * (W - 1), y0 + 0.5 * (H - 1), z_offset])
+        r0 = float(np.linalg.norm(lights[:, :3] - centre, axis=1).mean())
+    lo, hi = _robust_window(I, lo, hi)
+    dev = I.device
+    lead = I.dim() == 4
+    if height is not None:
+        _require_cuda(height, "height")
+        if height.dtype != torch.float32 or height.numel() != P:
+            raise ValueError(f"height must be float32 with {P} elements; got {height.dtype} {tuple(height.shape)}")
+        height = height.contiguous()
+    normals = _coef_empty(1, P, 3, nl, torch.float32, dev)
+    albedo = torch.empty((C, P), dtype=torch.float32, device=dev)
+    kind = torch.empty((1, P), dtype=torch.uint8, device=dev) if return_kind else None
+    res = torch.empty((C, P), dtype=torch.float32, device=dev) if return_res else None
+    kept = torch.empty((C, P), dtype=torch.int32, device=dev) if return_kept else None
+    fallback = torch.zeros(1, dtype=torch.int32, device=dev) if isinstance(stats, dict) else None
+    lights_dev = torch.as_tensor(lights, device=dev).contiguous()
+    I3 = _stack3(I, C, N, P)
+
+    def launch(h):
+        photometric_stereo_near_into(lights_dev, I3, H, W, normals, albedo, kind, res, kept, fallback, lo=lo, hi=hi,
+                                     min_lights=3 if min_lights is None else min_lights, origin=(x0, y0), height=h,
+                                     z_offset=z_offset, falloff=falloff, r0=r0, iters=iters,
+                                     delta=0.0 if delta is None else delta, weights=weights, normal_layout=nl,
+                                     kernel=kernel)
+
+    launch(height)
+    if refine:
+        kw = dict(height_kw or {})
+        ws = height_workspace(H, W, kw.get("precond", "multigrid"), dev)
+        hbuf = torch.empty((H, W), dtype=torch.float32, device=dev)
+        n_map = normals[0].reshape((H, W, 3) if nl == L.RTI_NORMAL_PIXEL_MAJOR else (3, H, W))
+        for _ in range(refine):
+            height_from_normals_into(n_map, ws, hbuf, layout=nl, **kw)
+            if fallback is not None:
+                fallback.zero_()
+            launch(hbuf)
+        height = hbuf
+    if fallback is not None:
+        stats["fallback_px"] = int(fallback.item())
+    alb = _unflatten(albedo, spatial, lead)
+    out = [_unflatten(normals, spatial, False, nl), alb.movedim(0, -1).contiguous() if lead else alb]
+    if return_kind:
+        out.append(_unflatten(kind, spatial, False))
+    out += [_unflatten(t, spatial, lead) for t in (res, kept) if t is not None]
+    if return_height:
+        out.append(torch.zeros((H, W), dtype=torch.float32, device=dev) if height is None else height.reshape(H, W))
+    return tuple(out)
+
+
 def fit_accumulate_into(R_dev, I3, state, *, k, init=False, light_stride=None):
     """Launch ``rti_fit_accumulate`` on preallocated tensors (no allocation, graph-capturable): add the chunk's
     B light planes to the fit state.

@@ -1,5 +1,5 @@
 """PyTorch custom ops over the C ABI: ``torch.ops.rti.fit_shared`` / ``fit_shared_residual`` /
-``fit_robust`` / ``photometric_stereo`` / ``fit_accumulate`` / ``fit_accum_solve`` / ``fit_residual`` / ``relight`` /
+``fit_robust`` / ``photometric_stereo`` / ``photometric_stereo_near`` / ``fit_accumulate`` / ``fit_accum_solve`` / ``fit_residual`` / ``relight`` /
 ``ptm_normals`` / ``relight_enhanced`` / ``map_unsharp`` / ``shade_normals`` / ``lrgb_from_rgb`` / ``relight_lrgb`` /
 ``lrgb_quantise`` / ``relight_lrgb8`` / ``hsh_quantise`` / ``relight_hsh8`` / ``hsh_normals`` / ``hsh8_normals`` /
 ``rgb8_quantise`` / ``relight_rgb8`` / ``rgb8_normals`` / ``relight_lrgb_enhanced`` / ``relight_lrgb8_enhanced`` /
@@ -189,6 +189,41 @@ def photometric_stereo(A: torch.Tensor, I: torch.Tensor, lo: float, hi: float, m
 
 @photometric_stereo.register_fake
 def _(A, I, lo, hi, min_lights, iters=0, delta=0.0, weights=None, planar=False, kernel=0):
+    return _ps_outputs(I, _lead(I), I.shape[-1], planar)
+
+
+@torch.library.custom_op("rti::photometric_stereo_near", mutates_args=())
+def photometric_stereo_near(lights: torch.Tensor, I: torch.Tensor, H: int, W: int, lo: float, hi: float,
+                            min_lights: int, iters: int = 0, delta: float = 0.0,
+                            weights: Optional[Sequence[float]] = None, planar: bool = False, kernel: int = 0,
+                            x0: float = 0.0, y0: float = 0.0, height: Optional[torch.Tensor] = None,
+                            z_offset: float = 0.0, falloff: bool = True,
+                            r0: float = 1.0) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor,
+                                                      torch.Tensor, torch.Tensor]:
+    """Near-light photometric stereo (``rti_photometric_stereo_near``): ``photometric_stereo`` with a row per pixel
+    from the light positions.  lights fp64 CUDA [N, 4] (``rti.ps_near_lights``), I CUDA [N, H·W] or [3, N, H·W];
+    pixel y·W + x sits at (x0 + x, y0 + y, z_offset + height), height fp32 [H·W] or None.  The outputs are
+    ``photometric_stereo``'s."""
+    api._require_cuda(I, "I")
+    api._require_cuda(lights, "lights")
+    if lights.dtype != torch.float64:
+        raise ValueError("lights must be float64 (rti.ps_near_lights)")
+    _same_device(lights=lights, I=I, **({} if height is None else {"height": height}))
+    _in_dtype(I)
+    I3 = _batched(I)
+    C, N, P = I3.shape
+    normals, albedo, kind, res, kept, fallback = _ps_outputs(I, (C,), P, planar)
+    api.photometric_stereo_near_into(lights.contiguous(), I3, H, W, normals, albedo, kind, res, kept, fallback, lo=lo,
+                                     hi=hi, min_lights=min_lights, origin=(x0, y0),
+                                     height=None if height is None else height.contiguous(), z_offset=z_offset,
+                                     falloff=falloff, r0=r0, iters=iters, delta=delta, weights=weights,
+                                     normal_layout="planar" if planar else "pixel", kernel=kernel)
+    return (normals,) + _unbatched(I, albedo) + (kind,) + _unbatched(I, res, kept) + (fallback,)
+
+
+@photometric_stereo_near.register_fake
+def _(lights, I, H, W, lo, hi, min_lights, iters=0, delta=0.0, weights=None, planar=False, kernel=0, x0=0.0, y0=0.0,
+      height=None, z_offset=0.0, falloff=True, r0=1.0):
     return _ps_outputs(I, _lead(I), I.shape[-1], planar)
 
 
